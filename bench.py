@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- benchmarks of the sketch engine on MI355X (one JSON line on stdout, printed by rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts its own ranks (one process per GPU,
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...``); launched under
@@ -21,9 +21,21 @@ stream) BEFORE the timed region, i.e. they are resident in HBM when the clock st
   cfg5  BloomFilter(224044920, 0.01) -> m = 2^31 bits (256 MiB per replica).  N_total keys (default 10^9) are split by
         key range over the ranks; STEP = clear + insert the shard + allreduce(OR) + check the shard.  Strong scaling.
 
-The default run (--gpus 1, cfg2) ALSO executes short steps of cfg3 (as written: 100M updates in 10 passes), cfg4 and cfg5
-(N = 1) after the headline's timed region and reports them under `configs.cfg3|cfg4|cfg5` (own ms_per_step, roofline,
-parity flags), so that the driver's one line covers the whole of BASELINE.json's metric (--no-extra-configs skips them).
+A plain run does only what its headline figure needs: set-up, spin-up and warm-up, EXACTLY --steps timed steps (one block
+between two fences; --repeats R times that many), the outputs of the last timed step if --dump-outputs is given, and the
+result line.  `ms_per_step` is the wall time of the timed block over --steps.
+
+--full adds everything else the benchmark measures or checks, after the timed region: the per-phase instrumented pass, the
+parity properties, the side measurements (CMS / CBF / GUPS / PCIe-inclusive / per-key latencies), the multi-GPU diagnostics
+and the scaling model, the host baselines, and the full result object in the detail file.  A full run with --gpus 1 and cfg2
+ALSO executes short steps of cfg3 (as written: 100M updates in 10 passes), cfg4 and cfg5 (N = 1) and reports them under
+`configs.cfg3|cfg4|cfg5` (own ms_per_step, roofline, parity flags), so that one line covers the whole of BASELINE.json's
+metric (--no-extra-configs skips them).
+
+--dump-outputs DIR: after the timed steps, what the last one computed is written as DIR/<name>.npy (float32 for membership
+answers, float64 for table words and counters, exact): the whole array when it has at most 2^20 elements, else 2^20 positions
+drawn with a fixed seed -- 12 MB at most per configuration.  The inputs are generated from a fixed seed, so two builds run
+with the same arguments can be compared output for output.  Rank 0 writes its own outputs.
 
 Failure handling: every rank arms a watchdog (--timeout seconds); a rank that fails or hangs still makes rank 0 (or the
 self-launching parent) print ONE JSON line with `"rc" != 0` and `"error"`, never a silent hang.
@@ -32,7 +44,7 @@ Per-rank memory, `--config cfg5 --gpus 8`: 125M keys x 16 B = 2.0 GB of resident
 partition scratch per 2^25-key chunk (bucket buffer ~1.1 GB insert / ~1.9 GB lookup, segment counts) + 0.5 GB of merge
 buffers: < 6 GB of the 288 GB.  At N = 1 the 10^9 keys are 16 GB.
 
-Every line carries
+Every line carries (the side operations' `rooflines` and `cpu_baseline` with --full only)
   roofline      the dominant kernel of the configuration (cfg2: the Bloom insert launch = k_part_bins + k_bloom_apply):
                 ALGORITHMIC bytes (72 B per inserted key, 45 per Bloom lookup, 60 per CMS update, ...) divided
                 by the launch time measured with HIP events on the launch stream, against the 8 TB/s HBM peak.
@@ -83,8 +95,12 @@ def parse():
     ap.add_argument("--batch", type=int, default=1_000_000, help="cfg4: keys per batch")
     ap.add_argument("--batches", type=int, default=50, help="cfg4: batches per step")
     ap.add_argument("--spinup", type=float, default=1.0, help="seconds of untimed steps before warm-up (clock ramp)")
-    ap.add_argument("--repeats", type=int, default=5, help="the block of --steps timed steps is run this many times, each between its own fences; "
-                    "`ms_per_step` / `value` are the MEDIAN block's, min / max are reported next to it")
+    ap.add_argument("--repeats", type=int, default=None, help="the block of --steps timed steps is run this many times (default 1), each between its "
+                    "own fences; `ms_per_step` / `value` are the MEDIAN block's, min / max are reported next to it")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: instrumented pass, parity checks, side "
+                    "measurements, extra configurations, host baselines, multi-GPU diagnostics, detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float32 / float64; "
+                    "arrays over 2^20 elements as a fixed, seeded sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--print-detail", action="store_true", help="also print the FULL result object (the one written to gpurun_out/bench_detail.json) on stderr")
     ap.add_argument("--no-detail", action="store_true", help="skip the CMS / CBF / GUPS side measurements")
@@ -531,6 +547,10 @@ class Cfg2:
         for _ in range(min(self.args.steps, 10)):
             self.step(True, every_phase=True)
 
+    def outputs(self):
+        """what the last step computed: the lookup's answers and the filter's table (32-bit words)"""
+        return {"check": ([self.state["res"]], "bool"), "table": ([table_words(self.blm)], "u32")}
+
     def rank_times(self):
         """(insert ms, merge ms, lookup ms, table bytes) of ONE un-overlapped step on this rank (multi_gpu_diagnostics)"""
         torch, blm, keys = self.ctx.torch, self.blm, self.keys
@@ -558,10 +578,11 @@ class Cfg2:
 
     def finish(self, ms_step):
         ctx, args, n, torch, timer, blm = self.ctx, self.args, self.n, self.ctx.torch, self.timer, self.blm
-        ok = bool(self.state["res"].all().item())  # every inserted key must be found (size-independent parity property)
-        bits_set = blm._cnt_number_bits_set()
+        # every inserted key must be found (size-independent parity property; --full)
+        ok = bool(self.state["res"].all().item()) if args.full else None
+        bits_set = blm._cnt_number_bits_set() if args.full else None
         merged_ok = None
-        if ctx.distributed:
+        if ctx.distributed and args.full:
             # multi-GPU parity, outside the timed region: the merged replica must equal ONE filter fed every rank's keys
             ref = self.pa.BloomFilter(est_elements=28005615, false_positive_rate=0.01, device=ctx.dev)
             for r in range(ctx.world):
@@ -589,7 +610,7 @@ class Cfg2:
                 n, chk_ms, "pass 1 is the insert's (hash + LDS counting sort, 2.67-byte probes); pass 2 streams the probes back "
                 "from the Infinity Cache against an LDS-resident slice")
         rooflines = {k: v for k, v in launches.items() if k != "bloom_insert"}
-        if ctx.rank == 0 and ctx.world == 1 and not args.no_detail:
+        if ctx.rank == 0 and ctx.world == 1 and args.full and not args.no_detail:
             side, rl = side_measurements(ctx, n, blm, self.keys)
             detail.update(side)
             rooflines.update(rl)
@@ -614,7 +635,7 @@ class Cfg2:
             "rooflines": rooflines, "detail": detail,
         }
         fails = []
-        if not ok:
+        if ok is False:
             fails.append("parity property violated: an inserted key was not found")
         if merged_ok is False:
             fails.append("parity property violated: the merged table differs from the single-stream filter")
@@ -788,21 +809,26 @@ class Cfg3:
     def instrumented(self):
         pass
 
+    def outputs(self):
+        """what the last step computed: the sketch's counters"""
+        return {"table": ([table_words(self.cms)], "i32")}
+
     def finish(self, ms_step):
-        ctx, torch, n, cms = self.ctx, self.ctx.torch, self.n, self.cms
-        # parity properties over the whole stream (the cell-by-cell compare with the oracle is tests/test_gpu_fullsize.py):
-        # every update lands once per row; elements_added is the sum of the weights
-        wsum = sum(int(w.to(torch.int64).sum().item()) for w in self.w)
-        if ctx.dist is not None:
-            tt = torch.tensor([wsum], dtype=torch.int64, device=f"cuda:{ctx.dev}")
-            ctx.dist.all_reduce(tt)
-            wsum = int(tt.item())
+        ctx, torch, n, cms, full = self.ctx, self.ctx.torch, self.n, self.cms, self.args.full
         els = cms.elements_added
-        total = int(cms.table_tensor[: 5 * 2**20].to(torch.int64).sum().item())
-        ok = els == wsum and total == 5 * wsum and cms.batch_diagnostics()["saturated"] == 0
+        ok, prefix_ok = None, None
+        if full:
+            # parity properties over the whole stream (the cell-by-cell compare with the oracle is tests/test_gpu_fullsize.py):
+            # every update lands once per row; elements_added is the sum of the weights
+            wsum = sum(int(w.to(torch.int64).sum().item()) for w in self.w)
+            if ctx.dist is not None:
+                tt = torch.tensor([wsum], dtype=torch.int64, device=f"cuda:{ctx.dev}")
+                ctx.dist.all_reduce(tt)
+                wsum = int(tt.item())
+            total = int(cms.table_tensor[: 5 * 2**20].to(torch.int64).sum().item())
+            ok = els == wsum and total == 5 * wsum and cms.batch_diagnostics()["saturated"] == 0
         # and a prefix against the oracle: one pass of 1M keys into a fresh sketch
-        prefix_ok = None
-        if ctx.rank == 0:
+        if full and ctx.rank == 0:
             sys.path.insert(0, str(ROOT / "oracle"))
             import numpy as np
             import oracle
@@ -814,7 +840,7 @@ class Cfg3:
             oc.add_keys(oracle.gen_keys16(0, m), oracle.gen_weights(0, m))
             prefix_ok = bool(np.array_equal(c2.table_tensor.cpu().numpy()[: oc.bins.size], oc.bins)) and c2.elements_added == oc.els_added
         add_ms = self.timer.mean_ms("add")
-        chk_ms = timed_loop(torch, lambda: cms.check_many(self.keys), 5)
+        chk_ms = timed_loop(torch, lambda: cms.check_many(self.keys), 5) if full else float("nan")
         line = {
             "metric": "million updates/sec (CMS 2^20 x 5, 100M weighted adds)",
             "config": {"workload": "cfg3: CountMinSketch(width=2^20, depth=5): per rank per step clear + 100M weighted updates "
@@ -824,11 +850,11 @@ class Cfg3:
             "roofline": roofline("cms_add", "CMS weighted add = k_part_bins<...,IdxCms<pow2>,PayWeightSmall,...,5> (weights 0..15 as 20-bit fields; k_part_scatter<PayWeight> otherwise) (sums the weights) + k_tally_fold + k_counter_apply "
                                  "(one pass of 10M updates between two HIP events)", n, add_ms,
                                  "pass 1 (5 FNV-1a chains + LDS counting sort), pass 2 folds 2^15-cell slices", "cms_add_weighted"),
-            "rooflines": {"cms_check": roofline("cms_check", "CMS lookup (min over 5 rows)", n, chk_ms, "see DESIGN.md 3.2")},
-            "detail": {"add_Mupd_s": n / add_ms / 1e3, "check_Mkeys_s": n / chk_ms / 1e3, "elements_added": els,
+            "rooflines": {"cms_check": roofline("cms_check", "CMS lookup (min over 5 rows)", n, chk_ms, "see DESIGN.md 3.2")} if full else {},
+            "detail": {"add_Mupd_s": n / add_ms / 1e3, "check_Mkeys_s": n / chk_ms / 1e3 if full else None, "elements_added": els,
                        "sum_bins_equals_depth_x_weights": ok, "prefix_1M_equals_oracle": prefix_ok},
         }
-        fails = [] if ok and prefix_ok is not False else ["parity property violated (cfg3)"]
+        fails = [] if ok is not False and prefix_ok is not False else ["parity property violated (cfg3)"]
         return line, fails
 
 
@@ -877,6 +903,10 @@ class Cfg4:
     def instrumented(self):
         pass
 
+    def outputs(self):
+        """what the last step computed: the filter's counters (the step ends with a flush)"""
+        return {"table": ([table_words(self.cbf)], "u32")}
+
     @staticmethod
     def _opt(name):
         from pyprobables_amd import _native as N
@@ -887,9 +917,11 @@ class Cfg4:
         ctx, torch, cbf = self.ctx, self.ctx.torch, self.cbf
         expect = self.adds - self.removes
         els = cbf.elements_added
-        total = int(cbf.table_tensor.view(torch.int32).to(torch.int64).sum().item())
-        diag = cbf.batch_diagnostics()
-        ok = els == expect and total == 7 * expect and diag == {"violations": 0, "saturated": 0}
+        total, diag, ok = None, None, None
+        if self.args.full:
+            total = int(cbf.table_tensor.view(torch.int32).to(torch.int64).sum().item())
+            diag = cbf.batch_diagnostics()
+            ok = els == expect and total == 7 * expect and diag == {"violations": 0, "saturated": 0}
         ms = self.timer.mean_ms("stream")
         line = {
             "metric": "million ops/sec (CBF m=2^28 k=7, mixed add/remove stream in 1M-key batches)",
@@ -910,10 +942,10 @@ class Cfg4:
                                  # (profiles/r06_pmc_traffic.json: "cfg4_stream" = the default API's update windows -- key copies + pass 1 + k_win_fold --, "..._borrow_keys" = the same without copies)
                                  {True: "cfg4_stream_combine", "borrow": "cfg4_stream_combine_borrow", "off": "cfg4_stream_nocombine", "window": "cfg4_stream", "window_borrow": "cfg4_stream_borrow_keys"}[self.mode]),
             "rooflines": {},
-            "detail": {"elements_added": els, "expected_elements": expect, "sum_counters_equals_k_x_live": total == 7 * expect, "diagnostics": diag,
-                       "update_window_folds": self._opt("update_window_folds"), "update_window_replays": self._opt("update_window_replays")},
+            "detail": {"elements_added": els, "expected_elements": expect, "sum_counters_equals_k_x_live": None if total is None else total == 7 * expect,
+                       "diagnostics": diag, "update_window_folds": self._opt("update_window_folds"), "update_window_replays": self._opt("update_window_replays")},
         }
-        return line, ([] if ok else ["parity property violated (cfg4)"])
+        return line, ([] if ok is not False else ["parity property violated (cfg4)"])
 
 
 # ----------------------------------------------------------------------------------------------- cfg5
@@ -952,6 +984,10 @@ class Cfg5:
     def instrumented(self):
         pass
 
+    def outputs(self):
+        """what the last step computed: the lookup's answers over the whole shard and the filter's table (32-bit words)"""
+        return {"check": (self.found, "bool"), "table": ([table_words(self.blm)], "u32")}
+
     def rank_times(self):
         """(insert ms, merge ms, lookup ms, table bytes) of one step on this rank (multi_gpu_diagnostics)"""
         torch, blm = self.ctx.torch, self.blm
@@ -978,10 +1014,10 @@ class Cfg5:
 
     def finish(self, ms_step):
         ctx, torch = self.ctx, self.ctx.torch
-        ok = all(bool(r.all().item()) for r in self.found)
+        ok = all(bool(r.all().item()) for r in self.found) if self.args.full else None
         # merged == single stream on a prefix (fresh filters; the full-size compare with the oracle is in tests/)
         merged_ok = None
-        if ctx.distributed:
+        if ctx.distributed and self.args.full:
             npre = 4_000_000
             lo, hi = self.parallel.shard_range(npre, ctx.rank, ctx.world)
             a = self.pa.BloomFilter(est_elements=224044920, false_positive_rate=0.01, device=ctx.dev)
@@ -1013,7 +1049,7 @@ class Cfg5:
                        "all_inserted_found": ok, "merged_prefix_equals_single_stream": merged_ok},
         }
         fails = []
-        if not ok:
+        if ok is False:
             fails.append("parity property violated: an inserted key was not found")
         if merged_ok is False:
             fails.append("parity property violated: merged prefix differs from the single-stream filter")
@@ -1096,8 +1132,9 @@ def multi_gpu_diagnostics(ctx: Ctx, args, wl):
                     "GPU sends (= receives) in the slice exchange + all_gather, divided by the slowest rank's merge time"}
 
 
-def run_workload(ctx: Ctx, args, name: str, steps: int, warmup: int, spinup: float, repeats: int = 1):
-    """spin-up, `warmup` untimed steps, `repeats` blocks of EXACTLY `steps` timed steps between two fences each, per-phase pass, parity.
+def run_workload(ctx: Ctx, args, name: str, steps: int, warmup: int, spinup: float, repeats: int = 1, dump=None):
+    """spin-up, `warmup` untimed steps, `repeats` blocks of EXACTLY `steps` timed steps between two fences each, the last step's outputs
+    written to `dump` (rank 0), and with --full the per-phase pass and the parity checks.
     -> (workload, body, fails, seconds per step of the median block (max over ranks), untimed spin-up steps)"""
     torch = ctx.torch
     phase(f"{name}: set-up (keys, sketch)")
@@ -1133,15 +1170,19 @@ def run_workload(ctx: Ctx, args, name: str, steps: int, warmup: int, spinup: flo
         blocks.append(ctx.max_over_ranks(time.perf_counter() - t0))
     srt = sorted(blocks)
     elapsed = srt[len(srt) // 2] if len(srt) % 2 else 0.5 * (srt[len(srt) // 2 - 1] + srt[len(srt) // 2])
-    phase(f"{name}: per-phase instrumented pass")
-    wl.instrumented()  # per-phase HIP-event times (not part of `value`)
-    ctx.fence()
+    if dump and ctx.rank == 0:
+        phase(f"{name}: writing the outputs")
+        dump_outputs(torch, wl.outputs(), dump)
+    if args.full:
+        phase(f"{name}: per-phase instrumented pass")
+        wl.instrumented()  # per-phase HIP-event times (not part of `value`)
+        ctx.fence()
     phase(f"{name}: parity checks and result")
     body, fails = wl.finish(elapsed / steps * 1e3)
-    if ctx.distributed and hasattr(wl, "rank_times"):
+    if args.full and ctx.distributed and hasattr(wl, "rank_times"):
         phase(f"{name}: per-rank diagnostics")
         body["multi_gpu"] = multi_gpu_diagnostics(ctx, args, wl)
-    if name in ("cfg2", "cfg5") and ctx.rank == 0:
+    if args.full and name in ("cfg2", "cfg5") and ctx.rank == 0:
         body["predicted"] = wl.predicted(body)
     body["config"]["timed_blocks"] = {
         "repeats": len(blocks), "steps_per_block": steps, "ms_per_step_median": elapsed / steps * 1e3, "ms_per_step_min": srt[0] / steps * 1e3,
@@ -1153,13 +1194,69 @@ def run_workload(ctx: Ctx, args, name: str, steps: int, warmup: int, spinup: flo
 def extra_config(ctx: Ctx, args, name: str):
     """one of cfg3 / cfg4 / cfg5 (N = 1) as written, a few steps: the object reported under `configs.<name>`"""
     steps, warmup = EXTRA_STEPS[name]
-    wl, body, fails, sec, spun = run_workload(ctx, args, name, steps, warmup, min(args.spinup, 0.3), repeats=min(args.repeats, 3))
+    wl, body, fails, sec, spun = run_workload(ctx, args, name, steps, warmup, min(args.spinup, 0.3), repeats=min(args.repeats or 3, 3))
     obj = {"metric": body.pop("metric"), "value": wl.ops_per_step / sec / 1e6, "unit": UNITS[name], "ms_per_step": sec * 1e3, "steps": steps,
            "warmup": warmup, "scaling": body.pop("scaling", "weak"), "dtype": DTYPES[name], "parity_ok": not fails, "parity_failures": fails}
     obj.update(body)
     del wl
     ctx.torch.cuda.empty_cache()
     return obj, fails
+
+
+# ----------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_SAMPLE = 1 << 20  # elements per written array: the whole output when it is no larger, else this many seeded positions
+
+
+def table_words(sketch):
+    """the sketch's table as the flat int32 tensor it lives in (logical part only), read where it lies: the engine is not told that
+    the table was handed out (``table_tensor`` would drop what it derived from it and change the steps that follow)"""
+    tab = sketch._tab
+    return tab.tensor[: (tab.logical_bytes + 3) // 4]
+
+
+def sample_positions(total: int, name: str):
+    """sorted positions of an output of `total` elements that --dump-outputs writes (None: all of them); a function of
+    (total, name) alone, so that every run and every build writes the same positions"""
+    import zlib
+
+    import numpy as np
+
+    if total <= DUMP_SAMPLE:
+        return None
+    rng = np.random.default_rng([SEED, zlib.crc32(name.encode())])
+    return np.unique(rng.integers(0, total, DUMP_SAMPLE, dtype=np.int64))
+
+
+def dump_outputs(torch, outputs: dict, where) -> dict:
+    """outputs: name -> (flat tensors read as ONE array, kind); kind "bool" is written as float32, "i32" / "u32" (32-bit words read
+    signed / unsigned) as float64, both exact.  -> {name: elements written to <where>/<name>.npy}"""
+    import numpy as np
+
+    out = Path(where)
+    out.mkdir(parents=True, exist_ok=True)
+    written = {}
+    for name, (parts, kind) in outputs.items():
+        parts = [t.reshape(-1) for t in parts]
+        pos = sample_positions(sum(t.numel() for t in parts), name)
+        if pos is None:
+            vals = torch.cat(parts)
+        else:
+            picked, lo = [], 0
+            for t in parts:
+                a, b = np.searchsorted(pos, [lo, lo + t.numel()])
+                if b > a:
+                    picked.append(t.index_select(0, torch.from_numpy(pos[a:b] - lo).to(t.device)))
+                lo += t.numel()
+            vals = torch.cat(picked)
+        if kind == "bool":
+            arr = vals.to(torch.float32)
+        elif kind == "u32":
+            arr = (vals.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)
+        else:
+            arr = vals.to(torch.float64)
+        np.save(out / f"{name}.npy", arr.cpu().numpy())
+        written[name] = int(arr.numel())
+    return written
 
 
 # ----------------------------------------------------------------------------------------------- the result line
@@ -1363,7 +1460,8 @@ def run(args):
         from pyprobables_amd import _native as _n
         name, _, value = opt.partition("=")
         _n.set_option(name, int(value, 0))
-    wl, body, fails, sec, spun = run_workload(ctx, args, args.config, args.steps, args.warmup, args.spinup, repeats=args.repeats)
+    wl, body, fails, sec, spun = run_workload(ctx, args, args.config, args.steps, args.warmup, args.spinup, repeats=args.repeats or 1,
+                                              dump=args.dump_outputs)
 
     line = {
         "metric": body.pop("metric"),
@@ -1377,7 +1475,7 @@ def run(args):
     line.update({"repeats": tb["repeats"], "ms_per_step_min": tb["ms_per_step_min"], "ms_per_step_max": tb["ms_per_step_max"]})
     body["config"]["clock_spinup"] = f"{spun} untimed steps (~{args.spinup:g} s) before the {args.warmup} warm-up steps"
     line.update(body)
-    if args.config == "cfg2" and ctx.world == 1 and not ctx.distributed and not args.no_extra_configs and not args.no_detail:
+    if args.full and args.config == "cfg2" and ctx.world == 1 and not ctx.distributed and not args.no_extra_configs and not args.no_detail:
         # the rest of BASELINE.json's metric on the same line: cfg3 as written (CMS 2^20 x 5, 100M weighted updates), and short
         # cfg4 / cfg5 (N = 1) steps -- after, and outside, the headline's timed region
         del wl
@@ -1399,7 +1497,7 @@ def run(args):
         fails += [f"cfg4 (borrow_keys): {x}" for x in f2]
         c3 = line["configs"]["cfg3"]
         line["cms"] = {"insert_Mupdates_s": c3["value"], "lookup_Mkeys_s": c3["detail"]["check_Mkeys_s"], "source": "configs.cfg3 (100M weighted updates in 10 passes; lookups of the 10M keys)"}
-    if ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
+    if ctx.rank == 0 and ctx.world == 1 and args.full and not args.no_cpu_baseline:
         if args.config == "cfg2":
             line["cpu_baseline"] = cpu_baseline(min(args.n, 10_000_000))
             if "configs" in line:  # the other halves of the metric: their own host legs (bounded to ~3 s each)
@@ -1428,7 +1526,7 @@ def run(args):
             ctypes.CDLL(None).fflush(None)
         except Exception:
             pass
-        where = write_detail(line)
+        where = write_detail(line) if args.full else None
         if args.print_detail:
             print(json.dumps(line), file=sys.stderr, flush=True)
         print(json.dumps(compact_line(line, args.config, where), separators=(",", ":")), flush=True)

@@ -12,9 +12,9 @@ for op in bloom_add bloom_check bloom_check_fresh cms_add cms_check cbf_add cbf_
   scripts/pmc_op.sh $op 10000000 5 > /dev/null 2>&1
   cp gpurun_out/pmc_$op.json "$OUT/"
 done
-python bench.py > "$OUT/bench_cfg2_default.json" 2> /dev/null
-python bench.py --steps 20 --warmup 5 > "$OUT/bench_cfg2_steps20.json" 2> /dev/null
-for c in cfg3 cfg4 cfg5; do python bench.py --config $c --no-cpu-baseline > "$OUT/bench_$c.json" 2> /dev/null; done
-python bench.py --config cfg4 --no-combine --no-cpu-baseline --steps 3 --warmup 1 > "$OUT/bench_cfg4_nocombine.json" 2> /dev/null
-PSK_BENCH_FORCE_DIST=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-detail > "$OUT/bench_cfg2_forced_dist_1rank.json" 2> /dev/null
+python bench.py --full > "$OUT/bench_cfg2_default.json" 2> /dev/null
+python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_cfg2_steps20.json" 2> /dev/null
+for c in cfg3 cfg4 cfg5; do python bench.py --full --config $c --no-cpu-baseline > "$OUT/bench_$c.json" 2> /dev/null; done
+python bench.py --full --config cfg4 --no-combine --no-cpu-baseline --steps 3 --warmup 1 > "$OUT/bench_cfg4_nocombine.json" 2> /dev/null
+PSK_BENCH_FORCE_DIST=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-detail > "$OUT/bench_cfg2_forced_dist_1rank.json" 2> /dev/null
 ls -la "$OUT"

@@ -32,9 +32,9 @@ done
 scripts/pmc_op.sh cfg4_stream 1000000 3 > /dev/null 2>&1
 cp gpurun_out/pmc_cfg4_stream.json "$OUT/"
 python scripts/make_pmc_json.py "$OUT" r05 > "$OUT/make_pmc_json.log" 2>&1
-python bench.py > "$OUT/bench_cfg2_default.json" 2> /dev/null
-python bench.py --steps 20 --warmup 5 > "$OUT/bench_cfg2_steps20.json" 2> /dev/null
-for c in cfg3 cfg4 cfg5; do python bench.py --config $c --no-cpu-baseline > "$OUT/bench_$c.json" 2> /dev/null; done
-python bench.py --config cfg4 --no-combine --no-cpu-baseline --steps 3 --warmup 1 > "$OUT/bench_cfg4_nocombine.json" 2> /dev/null
-PSK_BENCH_FORCE_DIST=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-detail > "$OUT/bench_cfg2_forced_dist_1rank.json" 2> /dev/null
+python bench.py --full > "$OUT/bench_cfg2_default.json" 2> /dev/null
+python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_cfg2_steps20.json" 2> /dev/null
+for c in cfg3 cfg4 cfg5; do python bench.py --full --config $c --no-cpu-baseline > "$OUT/bench_$c.json" 2> /dev/null; done
+python bench.py --full --config cfg4 --no-combine --no-cpu-baseline --steps 3 --warmup 1 > "$OUT/bench_cfg4_nocombine.json" 2> /dev/null
+PSK_BENCH_FORCE_DIST=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-detail > "$OUT/bench_cfg2_forced_dist_1rank.json" 2> /dev/null
 ls -la "$OUT"

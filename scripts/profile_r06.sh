@@ -18,8 +18,8 @@ for op in cbf_check cbf_check_kept cbf_add cbf_remove cms_check cms_add bloom_ch
   cp gpurun_out/trace_$op.txt "$OUT/rocprofv3_kernel_stats_$op.txt"
 done
 scripts/profile_r06_pmc.sh > "$OUT/pmc.log" 2>&1
-python bench.py --steps 20 --warmup 5 > "$OUT/bench_cfg2_default.json" 2> /dev/null
+python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_cfg2_default.json" 2> /dev/null
 cp gpurun_out/bench_detail.json "$OUT/bench_cfg2_default_detail.json"
-for c in cfg3 cfg4 cfg5; do python bench.py --config $c --no-cpu-baseline > "$OUT/bench_$c.json" 2> /dev/null; done
-PSK_BENCH_FORCE_DIST=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-detail > "$OUT/bench_cfg2_forced_dist_1rank.json" 2> /dev/null
+for c in cfg3 cfg4 cfg5; do python bench.py --full --config $c --no-cpu-baseline > "$OUT/bench_$c.json" 2> /dev/null; done
+PSK_BENCH_FORCE_DIST=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-detail > "$OUT/bench_cfg2_forced_dist_1rank.json" 2> /dev/null
 ls -la "$OUT"

@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/trace_bench_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o t -- python "$REPO/bench.py" --no-cpu-baseline "$@" > "$OUT.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o t -- python "$REPO/bench.py" --full --no-cpu-baseline "$@" > "$OUT.log" 2>&1
 cd "$REPO"
 python - "$OUT" <<'PY' > "$OUT.txt"
 import csv, glob, sys

@@ -56,3 +56,36 @@ def test_the_round_6_detail_object_keeps_the_per_key_latencies_on_the_line():
     assert len(text) < bench.LINE_LIMIT
     pk = json.loads(text)["detail"]["per_key_call_us"]
     assert set(pk) == {"bloom_check", "cms_add", "cms_check", "cbf_add", "cbf_check"} and all(0 < v < 100 for v in pk.values())
+
+
+def test_a_plain_run_is_lean_by_default(monkeypatch):
+    """without --full the run times exactly --steps steps once and measures nothing else; --full and --dump-outputs are options"""
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert args.steps == 7 and args.warmup == 2 and not args.full and args.dump_outputs is None and (args.repeats or 1) == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = bench.parse()
+    assert args.full and args.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_exact_seeded_samples(tmp_path):
+    """--dump-outputs: float32 answers, float64 words (read unsigned or signed), a fixed sample of large outputs read across chunks"""
+    torch = pytest.importorskip("torch")
+    import numpy as np
+
+    import bench
+
+    g = torch.Generator().manual_seed(1)
+    words = [torch.randint(-2**31, 2**31 - 1, (3 << 20,), dtype=torch.int32, generator=g), torch.arange(-5, 5, dtype=torch.int32)]
+    hits = [torch.rand(1000, generator=g) > 0.5]
+    got = bench.dump_outputs(torch, {"table": (words, "u32"), "check": (hits, "bool"), "small": (words[1:], "i32")}, tmp_path / "a")
+    bench.dump_outputs(torch, {"table": (words, "u32")}, tmp_path / "b")
+    table, check, small = (np.load(tmp_path / "a" / f"{k}.npy") for k in ("table", "check", "small"))
+    assert table.dtype == np.float64 and check.dtype == np.float32 and small.dtype == np.float64
+    pos = bench.sample_positions((3 << 20) + 10, "table")
+    assert got["table"] == pos.size <= bench.DUMP_SAMPLE and np.all(np.diff(pos) > 0)
+    flat = np.concatenate([w.numpy() for w in words]).view(np.uint32)
+    assert np.array_equal(table, flat[pos].astype(np.float64)) and np.array_equal(table, np.load(tmp_path / "b" / "table.npy"))
+    assert np.array_equal(check, hits[0].numpy().astype(np.float32)) and np.array_equal(small, np.arange(-5, 5, dtype=np.float64))

@@ -26,7 +26,7 @@ LINE_CAP = 8000  # the driver keeps the last ~8 KB of stdout: a longer last line
 
 
 def _run(cmd, env, timeout=900, tmp=None):
-    """-> (the compact line = the LAST line of stdout, the full object bench.py wrote to its detail file)"""
+    """-> (the compact line = the LAST line of stdout, the full object bench.py wrote to its detail file: --full runs only)"""
     detail = Path(tmp or "/tmp") / f"psk_bench_detail_{os.getpid()}.json"
     detail.unlink(missing_ok=True)
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=dict(env, PSK_BENCH_DETAIL=str(detail)), cwd=str(ROOT))
@@ -47,7 +47,7 @@ def test_two_ranks_merge_to_the_single_stream_filter(extra):
         pytest.skip("no GPU")
     env = dict(os.environ, PSK_BENCH_SINGLE_DEVICE="1")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--spinup", "0", "--keys-per-rank", "2000000", *extra]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--spinup", "0", "--keys-per-rank", "2000000", *extra]
     line, _ = _run(cmd, env)
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["cpu_baseline"] is None
     assert line["detail"]["all_inserted_found"] is True
@@ -63,7 +63,7 @@ def test_eight_ranks_on_one_device():
         pytest.skip("no GPU")
     env = dict(os.environ, PSK_BENCH_SINGLE_DEVICE="1")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--spinup", "0", "--keys-per-rank", "500000"]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "8", "--steps", "2", "--warmup", "1", "--spinup", "0", "--keys-per-rank", "500000"]
     line, full = _run(cmd, env)
     assert line["n_gpus"] == 8 and line["rc"] == 0 and line["detail"]["all_inserted_found"] is True
     assert line["detail"]["merged_table_equals_single_stream"] is True
@@ -72,7 +72,7 @@ def test_eight_ranks_on_one_device():
     assert mg["ranks_seen_by_rccl"] == 8 and [p["rank"] for p in mg["per_rank"]] == list(range(8))
     assert all(p["insert_ms"] > 0 and p["merge_ms"] > 0 and p["check_ms"] > 0 for p in mg["per_rank"])
     assert mg["merge_GBs_per_gpu"] > 0 and mg["table_bytes"] == 2**28 // 8
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--config", "cfg5", "--n-total", "8000003", "--steps", "1", "--warmup", "1", "--spinup", "0"]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "8", "--config", "cfg5", "--n-total", "8000003", "--steps", "1", "--warmup", "1", "--spinup", "0"]
     line, full = _run(cmd, env)
     assert line["n_gpus"] == 8 and line["detail"]["all_inserted_found"] is True and line["detail"]["merged_prefix_equals_single_stream"] is True
     assert line["multi_gpu"]["ranks_seen_by_rccl"] == 8 and len(full["multi_gpu"]["per_rank"]) == 8 and full["multi_gpu"]["table_bytes"] == 2**31 // 8
@@ -85,7 +85,7 @@ def test_launched_under_torch_distributed_run():
         pytest.skip("no GPU")
     env = dict(os.environ, PSK_BENCH_SINGLE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--spinup", "0",
+           "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--spinup", "0",
            "--keys-per-rank", "1000000"]
     line, _ = _run(cmd, env)
     assert line["n_gpus"] == 2 and line["detail"]["merged_table_equals_single_stream"] is True
@@ -99,7 +99,7 @@ def test_cfg5_two_ranks_through_the_real_allreduce_or():
         pytest.skip("no GPU")
     env = dict(os.environ, PSK_BENCH_SINGLE_DEVICE="1")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--config", "cfg5", "--n-total", "6000001", "--steps", "1", "--warmup", "1", "--spinup", "0"]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "2", "--config", "cfg5", "--n-total", "6000001", "--steps", "1", "--warmup", "1", "--spinup", "0"]
     line, _ = _run(cmd, env)
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
     assert line["detail"]["all_inserted_found"] is True and line["detail"]["merged_prefix_equals_single_stream"] is True
@@ -113,7 +113,7 @@ def test_other_configs_emit_a_valid_line(cfg, extra):
         pytest.skip("no GPU")
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--config", cfg, "--steps", "2", "--warmup", "1", "--spinup", "0", "--no-cpu-baseline", *extra]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--config", cfg, "--steps", "2", "--warmup", "1", "--spinup", "0", "--no-cpu-baseline", *extra]
     line, full = _run(cmd, env)
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["roofline"]["achieved"] > 0
     assert cfg in line["config"]["workload"] and len(line["roofline"]["kernel"]) <= 80
@@ -121,13 +121,13 @@ def test_other_configs_emit_a_valid_line(cfg, extra):
 
 
 def test_default_run_line_fits_the_drivers_tail():
-    """the driver's own command: the last stdout line must parse, carry roofline + cpu_baseline + the other three configurations, and fit"""
+    """the headline command with --full: the last stdout line must parse, carry roofline + cpu_baseline + the other three configurations, and fit"""
     torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
-    line, full = _run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"], env)
+    line, full = _run([sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "1", "--steps", "20", "--warmup", "5"], env)
     assert line["rc"] == 0 and line["n_gpus"] == 1 and line["steps"] == 20 and line["warmup"] == 5
     rf, cb = line["roofline"], line["cpu_baseline"]
     assert rf["bound"] == "hbm" and 0 < rf["frac"] < 1 and rf["peak"] == 8000.0 and rf["traffic"] and rf["avg_kernel_ms"] > 0
