@@ -115,6 +115,7 @@ int psk_device_count(int *count);
  *   "auto_combine" (s)          1        (update windows off) small unit add batches wait as scattered probes
  *   "combine_keys"              2^26     keys per list of psk_cbf_update_combined
  *   "merge_single_rank"         0        1: psk_merge_* run the collective path on a one-rank communicator (tests)
+ *   "lazy_clear"                1        psk_clear of a Bloom table the engine alone reads is deferred (psk_clear below); 0 = sweep at once
  *   per sketch only: "table_private" (below), read-only "window_pending_batches" (batches an update window still holds: PSK_DEVICE_BORROWED
  *   buffers among them must stay as they are).
  *
@@ -153,6 +154,11 @@ int psk_bloom_create(uint64_t m_bits, uint32_t k, int device, void *ext_table, p
 int psk_cbf_create(uint64_t m, uint32_t k, int device, void *ext_table, psk_sketch **out);
 int psk_cms_create(uint64_t width, uint32_t depth, int device, void *ext_table, psk_sketch **out);
 int psk_destroy(psk_sketch *s);                             /* ext_table: write-combined updates still waiting are applied first (NULL stream + sync) */
+/* psk_clear of a Bloom handle whose table nobody outside the engine holds (library-owned, or caller-owned with "table_private" = 1, and not
+ * handed out by psk_table_info(&ptr) since the last psk_rescan_bound) and option "lazy_clear" = 1 launches nothing: the table is marked
+ * clear-pending.  Every entry point that reads, writes or hands out the table, or reads the counters, runs the clear first on its own stream
+ * (psk_flush does nothing else for a Bloom handle); a large insert takes it over -- its first apply stores the slices whole.  Otherwise the
+ * table and the counter block are zeroed by one kernel on `stream`. */
 int psk_clear(psk_sketch *s, void *stream);                 /* bloom.py:217-221, countminsketch.py:240-244 */
 int psk_synchronize(psk_sketch *s, void *stream);
 int psk_release_scratch(psk_sketch *s);                     /* free staging + partition buffers (regrow on demand) */
@@ -161,7 +167,8 @@ int psk_release_scratch(psk_sketch *s);                     /* free staging + pa
  * lists (they hold waiting updates: psk_flush applies them), bytes[2] = of which the kept 4-bit images; no stream work, no synchronisation.
  * (The scratch is an implementation detail of the path behind countingbloom.py:135-208 / bloom.py:234-272: the reference has none.) */
 int psk_scratch_bytes(psk_sketch *s, uint64_t bytes[3]);
-/* device pointer + padded size + logical size (the reference's array byte length) */
+/* device pointer + padded size + logical size (the reference's array byte length).  A pending (deferred) clear runs first, on the NULL
+ * stream: call psk_flush on the stream that will use the pointer before this, so that the clear is ordered there. */
 int psk_table_info(psk_sketch *s, void **dev_ptr, uint64_t *padded_bytes, uint64_t *logical_bytes);
 /* copy the first nbytes of the table to / from host memory in the reference's byte layout
  * (array('B') LSB-first bits, array('I') uint32 LE, array('i') int32 LE row-major by depth):
@@ -242,6 +249,8 @@ int psk_cbf_check(psk_sketch *s, int layout, const void *data, const uint64_t *o
  * the raw table pointer (psk_table_info) to anything else call psk_flush.  remove = 0: add, 1: remove. */
 int psk_cbf_update_combined(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n,
                             uint32_t key_len, const uint32_t *weights, int remove, int where, void *stream);
+/* applies everything that waits in the engine on `stream`: the write-combined CBF updates above and a deferred Bloom clear (psk_clear).
+ * Call it before reading or writing the table through a pointer from psk_table_info. */
 int psk_flush(psk_sketch *s, void *stream);
 /* Ordered (one-at-a-time, in sequence) execution of the reference semantics on the GPU, including
  * each op's return value: exact for ANY stream.  weights int64[n] or NULL (=1); opmode psk_opmode. */

@@ -158,7 +158,7 @@ extern "C" int psk_destroy(psk_sketch *s)
     if (s->lk.dev) hipFree(s->lk.dev);
     if (s->lk.pin) hipHostFree((void *)s->lk.pin);
     if (s->wt.pin) hipHostFree((void *)s->wt.pin);
-    for (DevBuf *b : {&s->s_keys, &s->s_offs, &s->s_w, &s->s_out, &s->s_aux, &s->s_part, &s->s_cnt, &s->s_flag, &s->s_tflag, &s->s_part2, &s->s_cnt2, &s->s_merge, &s->s_vals, &s->s_perm, &s->s_run, &s->s_tally,
+    for (DevBuf *b : {&s->s_keys, &s->s_offs, &s->s_w, &s->s_out, &s->s_aux, &s->s_part, &s->s_cnt, &s->s_flag, &s->s_spill, &s->s_tflag, &s->s_part2, &s->s_cnt2, &s->s_merge, &s->s_vals, &s->s_perm, &s->s_run, &s->s_tally,
                       &s->comb.add.keys, &s->comb.add.w, &s->comb.rem.keys, &s->comb.rem.w, &s->scat.add.part, &s->scat.add.cnt, &s->scat.rem.part, &s->scat.rem.cnt, &s->s_brw, &s->shadow.img,
                       &s->win.keys, &s->s_snap, &s->s_wstat, &s->s_phase}) {
         if (b->p) hipFree(b->p);
@@ -233,6 +233,27 @@ static __global__ __launch_bounds__(kBlock) void k_clear(uint4 *tab, uint64_t nv
 
 static int scat_drop(psk_sketch *s, hipStream_t st);  // forget the scattered write-combined updates (defined with them below)
 
+int64_t g_lazy_clear = 1;  // psk_set_option("lazy_clear", 0): every psk_clear sweeps the table at once (A/B of the deferred clear)
+
+// one launch for the table AND the counter block (two fills are two ~5 us launches; clear sits in every bench step)
+static int launch_clear(psk_sketch *s, hipStream_t st)
+{
+    const uint64_t nvec = s->padded_bytes / 16;
+    uint64_t grid = (nvec + kBlock * 4 - 1) / (kBlock * 4);
+    if (grid > 2048) grid = 2048;
+    if (grid == 0) grid = 1;
+    hipLaunchKernelGGL(k_clear, dim3((unsigned)grid), dim3(kBlock), 0, st, (uint4 *)s->table, nvec, s->ctr);
+    HIP_TRY(hipGetLastError());
+    return PSK_OK;
+}
+
+int clear_materialize(psk_sketch *s, hipStream_t st)
+{
+    if (!s->clear_pending) return PSK_OK;
+    s->clear_pending = false;
+    return launch_clear(s, st);
+}
+
 extern "C" int psk_clear(psk_sketch *s, void *stream)
 {
     CHECK_HANDLE(s, -1);
@@ -244,14 +265,15 @@ extern "C" int psk_clear(psk_sketch *s, void *stream)
     s->win.n = s->win.copied = 0;  // (the update window too; a window's back-off is a property of the stream and stays)
     s->win.batches.clear();
     PSK_TRY(scat_drop(s, st));
-    // one launch for the table AND the counter block (two fills are two ~5 us launches; clear sits in every bench step)
-    const uint64_t nvec = s->padded_bytes / 16;
-    uint64_t grid = (nvec + kBlock * 4 - 1) / (kBlock * 4);
-    if (grid > 2048) grid = 2048;
-    if (grid == 0) grid = 1;
-    hipLaunchKernelGGL(k_clear, dim3((unsigned)grid), dim3(kBlock), 0, st, (uint4 *)s->table, nvec, s->ctr);
-    HIP_TRY(hipGetLastError());
-    return PSK_OK;
+    // Bloom table that nobody outside the engine reads: the sweep is deferred.  The next entry point that reads, writes or hands out the
+    // table runs it first on its own stream (clear_materialize), except a single-level partitioned insert, whose first apply STORES its
+    // slices instead of read-modify-writing them (psk_part_bloom_add.hip): the 32 MiB of zeros are then neither written nor read back.
+    if (s->kind == PSK_KIND_BLOOM && g_lazy_clear != 0 && !s->shadow.exposed && (s->owns_table || s->table_private)) {
+        s->clear_pending = true;
+        return PSK_OK;
+    }
+    s->clear_pending = false;
+    return launch_clear(s, st);
 }
 
 extern "C" int psk_synchronize(psk_sketch *s, void *stream)
@@ -266,6 +288,10 @@ extern "C" int psk_table_info(psk_sketch *s, void **dev_ptr, uint64_t *padded_by
 {
     if (!s) return fail(PSK_EINVAL, "sketch handle is NULL");
     ++s->table_version;  // the pointer leaves the engine: whoever holds it may write
+    if (s->clear_pending) {  // (no stream here: a deferred clear runs on the null stream -- psk_flush on the caller's stream first avoids it)
+        PSK_USE_DEVICE(s->device);
+        PSK_TRY(clear_materialize(s, nullptr));
+    }
     if (dev_ptr) s->shadow.exposed = true;  // ... and later, too: no kept images until the holder says it is done (psk_rescan_bound)
     if (dev_ptr) *dev_ptr = s->table;
     if (padded_bytes) *padded_bytes = s->padded_bytes;
@@ -296,6 +322,7 @@ extern "C" int psk_write_table(psk_sketch *s, const void *src_host, uint64_t nby
     s->win.n = s->win.copied = 0;
     s->win.batches.clear();
     PSK_TRY(scat_drop(s, st));
+    s->clear_pending = false;  // (the fills below do what the deferred clear would)
     HIP_TRY(hipMemsetAsync(s->table, 0, s->padded_bytes, st));
     HIP_TRY(hipMemcpyAsync(s->table, src_host, nbytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(s->ctr, 0, sizeof(long long) * PSK_CTR_COUNT, st));
@@ -647,6 +674,7 @@ const OptDesc kOptions[] = {
     {"cms_small_weights", &g_small_weights, kOptSupported, kAny},
     {"pass1_bins", &g_part_bins, kOptSupported, kAny},
     {"merge_single_rank", &g_merge_single_rank, kOptSupported, kAny},
+    {"lazy_clear", &g_lazy_clear, kOptSupported, kAny},
     // thresholds of the path choice, test hooks
     {"partition_two_level_slices", &g_part_two_level_slices, kOptThreshold, kAny},
     {"auto_combine_keys", &g_auto_combine_keys, kOptThreshold, kAny},
@@ -733,6 +761,10 @@ extern "C" int psk_sketch_set_option(psk_sketch *s, const char *name, int64_t va
         s->table_private = value != 0;
         if (s->table_private) s->shadow.exposed = false;  // (from here on the holder announces its writes)
         else if (!s->owns_table) s->shadow.exposed = true;
+        if (s->shadow.exposed && s->clear_pending) {  // the holder may read its table at any time from here on (null stream: no stream here)
+            PSK_USE_DEVICE(s->device);
+            PSK_TRY(clear_materialize(s, nullptr));
+        }
         ++s->table_version;
         return PSK_OK;
     }
@@ -785,6 +817,7 @@ extern "C" int psk_bloom_add(psk_sketch *s, int layout, const void *data, const 
     bool done = false;
     if (!s->pend.active) PSK_TRY(bloom_add_partitioned(s, b, st, &done));  // (a pending split lookup owns the bucket buffer)
     if (done) return finish(where, nullptr, st);
+    PSK_TRY(clear_materialize(s, st));  // (the partitioned insert consumes a deferred clear; the direct kernel ORs into the table)
     Mailbox mb;  // (an update returns nothing, but a PSK_HOST call ends when the kernel has read the caller's keys: the same mailbox says so)
     PSK_TRY(mailbox_arm(s, where, n, true, &mb));
     KeysInline64 ik;
@@ -802,6 +835,7 @@ extern "C" int psk_bloom_check(psk_sketch *s, int layout, const void *data, cons
     PSK_TRY(check_hashes_width(s, layout, key_len));
     if (n && !out) return fail(PSK_EINVAL, "out is NULL");
     hipStream_t st = (hipStream_t)stream;
+    PSK_TRY(clear_materialize(s, st));
     Batch b;
     PSK_TRY(stage_batch(s->s_keys, s->s_offs, layout, data, offsets, n, key_len, where, st, &b));
     OutBuf o;
@@ -852,6 +886,7 @@ extern "C" int psk_bloom_check_begin(psk_sketch *s, int layout, const void *data
     b.n = n;
     b.key_len = key_len;
     if (n && !data) return fail(PSK_EINVAL, "keys are NULL");
+    PSK_TRY(clear_materialize(s, (hipStream_t)stream));  // (begin never reads the table, the finish on the same stream does)
     return bloom_check_begin_partitioned(s, b, (hipStream_t)stream);
 }
 
@@ -863,6 +898,7 @@ extern "C" int psk_bloom_check_finish(psk_sketch *s, uint8_t *out_dev, void *str
     const Batch b = s->pend.b;
     if (b.n && !out_dev) return fail(PSK_EINVAL, "out is NULL");
     hipStream_t st = (hipStream_t)stream;
+    PSK_TRY(clear_materialize(s, st));  // (a clear between begin and finish)
     bool redo = false;
     PSK_TRY(bloom_check_finish_partitioned(s, out_dev, st, &redo));
     if (!s->pend.scattered) {  // batch / table not eligible for the partitioned path: plain direct lookup now
@@ -924,6 +960,7 @@ extern "C" int psk_bloom_check_bits(psk_sketch *s, int layout, const void *data,
     PSK_TRY(check_hashes_width(s, layout, key_len));
     if (n && (!out_bits || !hits)) return fail(PSK_EINVAL, "out_bits / hits is NULL");
     hipStream_t st = (hipStream_t)stream;
+    PSK_TRY(clear_materialize(s, st));
     Batch b;
     PSK_TRY(stage_batch(s->s_keys, s->s_offs, layout, data, offsets, n, key_len, where, st, &b));
     const uint64_t nwords = (n + 63) / 64;
@@ -1353,6 +1390,7 @@ static int win_append(psk_sketch *s, const void *data, uint64_t n, bool remove, 
 
 int flush_combined(psk_sketch *s, hipStream_t st)
 {
+    PSK_TRY(clear_materialize(s, st));  // (every caller is about to read the table or the counters, or to hand them out)
     if (s->kind != PSK_KIND_CBF) return PSK_OK;
     if (s->win.n) {  // (the window holds what arrived AFTER anything the older mechanisms below hold: see win_append's callers)
         ++s->table_version;
@@ -2170,7 +2208,7 @@ extern "C" int psk_scratch_bytes(psk_sketch *s, uint64_t bytes[3])
 {
     if (!s || !bytes) return fail(PSK_EINVAL, "psk_scratch_bytes: NULL argument");
     uint64_t all = 0, waiting = 0;
-    for (const DevBuf *b : {&s->s_keys, &s->s_offs, &s->s_w, &s->s_out, &s->s_aux, &s->s_part, &s->s_cnt, &s->s_flag, &s->s_tflag, &s->s_part2, &s->s_cnt2, &s->s_merge, &s->s_vals, &s->s_perm, &s->s_run, &s->s_tally,
+    for (const DevBuf *b : {&s->s_keys, &s->s_offs, &s->s_w, &s->s_out, &s->s_aux, &s->s_part, &s->s_cnt, &s->s_flag, &s->s_spill, &s->s_tflag, &s->s_part2, &s->s_cnt2, &s->s_merge, &s->s_vals, &s->s_perm, &s->s_run, &s->s_tally,
                             &s->comb.add.keys, &s->comb.add.w, &s->comb.rem.keys, &s->comb.rem.w, &s->scat.add.part, &s->scat.add.cnt, &s->scat.rem.part, &s->scat.rem.cnt, &s->s_brw, &s->shadow.img,
                             &s->win.keys, &s->s_snap, &s->s_wstat, &s->s_phase})
         if (b->p) all += b->cap;
@@ -2191,7 +2229,7 @@ extern "C" int psk_release_scratch(psk_sketch *s)
     ho_apply(s);  // (what is waiting is applied under this sketch's own options)
     PSK_TRY(flush_combined(s, nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    for (DevBuf *b : {&s->s_keys, &s->s_offs, &s->s_w, &s->s_out, &s->s_aux, &s->s_part, &s->s_cnt, &s->s_flag, &s->s_tflag, &s->s_part2, &s->s_cnt2, &s->s_merge, &s->s_vals, &s->s_perm, &s->s_run, &s->s_tally,
+    for (DevBuf *b : {&s->s_keys, &s->s_offs, &s->s_w, &s->s_out, &s->s_aux, &s->s_part, &s->s_cnt, &s->s_flag, &s->s_spill, &s->s_tflag, &s->s_part2, &s->s_cnt2, &s->s_merge, &s->s_vals, &s->s_perm, &s->s_run, &s->s_tally,
                       &s->comb.add.keys, &s->comb.add.w, &s->comb.rem.keys, &s->comb.rem.w, &s->scat.add.part, &s->scat.add.cnt, &s->scat.rem.part, &s->scat.rem.cnt, &s->s_brw, &s->shadow.img,
                       &s->win.keys, &s->s_snap, &s->s_wstat, &s->s_phase}) {
         if (b->p) HIP_TRY(hipFree(b->p));

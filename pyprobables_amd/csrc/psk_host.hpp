@@ -100,6 +100,7 @@ struct psk_sketch {
     bool pow2;
     void *table;
     bool owns_table;
+    bool clear_pending = false;  // Bloom: psk_clear deferred -- the table and the counter block read as zero, k_clear has not run yet (clear_materialize)
     uint64_t padded_bytes, logical_bytes;
     long long *ctr;    // device int64[PSK_CTR_COUNT]
     DevBuf s_keys, s_offs, s_w, s_out, s_aux;  // staging for PSK_HOST buffers
@@ -108,6 +109,7 @@ struct psk_sketch {
     uint32_t mbox_timeouts = 0, mbox_skipped = 0;  // polls in a row that gave up / calls since the handle stopped polling (mailbox_arm)
     DevBuf s_part, s_cnt;                      // partitioned path: bucket buffer + per-bucket fill counts
     DevBuf s_flag;                             // split lookup: "a segment overflowed" flag
+    DevBuf s_spill;                            // Bloom insert after a deferred clear: [0] count, then the bit indices of overflowing probes
     DevBuf s_tflag;                            // tile-flag Bloom lookups: one uint32 per pass-1 tile of a round; "flagged" = holds the round's
     uint32_t tflag_gen = 0;                    // generation number (never 0), so the flags are never reset
     uint32_t tflag_wgs = 0;  // pass-1 workgroups of the tile-flag lookup in progress (0: the shape's own count; tile_flag_geometry)
@@ -805,6 +807,7 @@ PSK_DECLARE_VARIANTS(int, cbf_check_partitioned, (psk_sketch *s, const Batch &b,
 // ONE set of instantiations (psk_part_cbf_check.hip) instead of one per caller.  *fits = false: a tile too large for 16-bit stage positions.
 PSK_DECLARE_VARIANTS(int, bloomidx_lookup_scatter, (psk_sketch *s, const Batch &sub, uint64_t cnt, uint32_t kk, PartGeom *g, uint32_t *flag, hipStream_t st, bool *handled, bool *fits))
 PSK_HIDDEN int flush_combined(psk_sketch *s, hipStream_t st);  // apply the write-combined CBF updates, if any (psk_capi.hip)
+PSK_HIDDEN int clear_materialize(psk_sketch *s, hipStream_t st);  // run the deferred clear of a Bloom table now, if one is pending (psk_capi.hip)
 // pass 1 of a unit-weight CBF batch, appended to the handle's persistent add (neg = 0) / decrement (neg = 1) list; *done = false:
 // the batch / table is not eligible (nothing was launched)
 PSK_DECLARE_VARIANTS(int, cbf_scat_append, (psk_sketch *s, const Batch &b, int neg, hipStream_t st, bool *done))

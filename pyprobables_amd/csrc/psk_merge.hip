@@ -131,6 +131,7 @@ extern "C" int psk_merge_or(psk_sketch *s, void *nccl_comm, void *stream)
     if (!nccl_comm) return fail(PSK_EINVAL, "communicator is NULL");
     PSK_USE_DEVICE(s->device);
     ++s->table_version;  // the merge rewrites the table (psk_sketch::shadow is stale from here on)
+    PSK_TRY(clear_materialize(s, (hipStream_t)stream));  // (a deferred clear lands before the exchange reads the table)
     Rccl *R;
     PSK_TRY(rccl(&R));
     ncclComm_t comm = (ncclComm_t)nccl_comm;

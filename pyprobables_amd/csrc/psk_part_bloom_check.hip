@@ -172,6 +172,10 @@ static bool tile_flag_geometry(psk_sketch *s, const Batch &b, PartGeom *g, uint6
     return true;
 }
 
+// the tile flags proper start 16 bytes into s_tflag: the word in front of them (tileflag[-1]) tells k_bloom_flag_resolve whether any is set
+static uint32_t *tflag_base(psk_sketch *s) { return (uint32_t *)s->s_tflag.p + 4; }
+constexpr uint32_t kResolveWgs = 256;
+
 // pass 1 of one round (keys [0, cnt) of `sub`); defer: split lookup, the table is not consulted
 static int tile_flag_scatter(psk_sketch *s, const Batch &sub, uint64_t cnt, bool defer, PartGeom *g, uint32_t *gen_out, hipStream_t st, bool *handled)
 {
@@ -179,8 +183,9 @@ static int tile_flag_scatter(psk_sketch *s, const Batch &sub, uint64_t cnt, bool
         using Src = decltype(src);
         return with_kt<Src>(s->k, [&](auto kt) {
             constexpr int KT = decltype(kt)::value;
-            // one flag per tile; tiles are at least 64 keys (evened tiles are multiples of 64)
-            const uint64_t flag_bytes = (cnt / 64 + 2048) * 4;
+            // one flag per tile; tiles are at least 64 keys (evened tiles are multiples of 64); 16 bytes in front: word 3 = "some tile
+            // of the round is flagged" (tileflag[-1] of the kernels: tflag_base)
+            const uint64_t flag_bytes = (cnt / 64 + 2048) * 4 + 16;
             if (flag_bytes > s->s_tflag.cap || s->tflag_gen == 0xFFFFFFFFu) {
                 PSK_TRY(ensure(s->s_tflag, flag_bytes));
                 HIP_TRY(hipMemsetAsync(s->s_tflag.p, 0, s->s_tflag.cap, st));  // once (and when the generation number wraps)
@@ -188,7 +193,7 @@ static int tile_flag_scatter(psk_sketch *s, const Batch &sub, uint64_t cnt, bool
             }
             const uint32_t gen = ++s->tflag_gen;
             *gen_out = gen;
-            SpillBloomFlag spill{(const uint32_t *)s->table, (uint32_t *)s->s_tflag.p, gen, defer ? 1u : 0u};
+            SpillBloomFlag spill{(const uint32_t *)s->table, tflag_base(s), gen, defer ? 1u : 0u};
             return launch_scatter<Src, IdxBloom<kTuPow2>, PayTileTag, SpillBloomFlag, KT>(s, src, IdxBloom<kTuPow2>{s->md}, PayTileTag{}, spill, g, cnt, st,
                                                                                           s->tflag_wgs);
         });
@@ -201,7 +206,7 @@ static int tile_flag_test(psk_sketch *s, const Batch &sub, uint64_t cnt, const P
     bool handled = false;
     PSK_TRY(with_part_source(sub, &handled, [&](auto src) {
         using Src = decltype(src);
-        uint32_t *tflag = (uint32_t *)s->s_tflag.p;
+        uint32_t *tflag = tflag_base(s);
         const size_t lds = (size_t)1 << (g.shift - 3);
         PSK_TRY(set_dyn_lds(k_bloom_test_flag, lds));
         hipLaunchKernelGGL(k_bloom_test_flag, dim3(g.nbuckets), dim3(kApplyThreads), lds, st, (const uint32_t *)s->table, s->padded_bytes / 4, g,
@@ -210,7 +215,9 @@ static int tile_flag_test(psk_sketch *s, const Batch &sub, uint64_t cnt, const P
         const uint64_t ntiles = (cnt + g.tile - 1) / g.tile;
         LookupPublish pub;
         if (publish_units && g_bloom_lookup == 2 && s->lk.dev) pub = LookupPublish{s->lk.dev, s->lk.pin, publish_units, 3};
-        hipLaunchKernelGGL((k_bloom_flag_resolve<Src, kTuPow2>), dim3((unsigned)(ntiles < 1024 ? ntiles : 1024)), dim3(kResolveThreads), 0, st, src,
+        // (a small grid: with no tile flagged -- the usual case of the batches this scheme is chosen for -- every workgroup leaves at once, and
+        // the launch is what remains of the kernel; 1024 workgroups cost ~5 us for nothing)
+        hipLaunchKernelGGL((k_bloom_flag_resolve<Src, kTuPow2>), dim3((unsigned)(ntiles < kResolveWgs ? ntiles : kResolveWgs)), dim3(kResolveThreads), 0, st, src,
                            (const uint32_t *)s->table, s->md, s->k, (const uint32_t *)tflag, gen, g.tile, cnt, out, pub);
         HIP_TRY(hipGetLastError());
         return (int)PSK_OK;

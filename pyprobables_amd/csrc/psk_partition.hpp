@@ -324,10 +324,22 @@ struct PayKeyId {
     __device__ __forceinline__ uint32_t operator()(uint64_t i, uint64_t base) const { return (uint32_t)(i - base); }
 };
 
-// fallback for a probe that cannot go through the bucket buffer: apply it straight to the table
+// fallback for a probe that cannot go through the bucket buffer: apply it straight to the table -- or, when the table waits for a
+// deferred clear that the apply's store mode performs (list != nullptr), append its bit index to list[2 ..] (list[0] = count): a bit
+// ORed into the table now would be overwritten by that store.  cap = the launch's probe count, so the list can never fill up.
 struct SpillBloomOr {
     uint32_t *tab;
-    __device__ __forceinline__ void operator()(uint32_t idx, uint32_t) const { atomicOr(tab + (idx >> 5), 1u << (idx & 31)); }
+    uint32_t *list = nullptr;
+    uint32_t cap = 0;
+    __device__ __forceinline__ void operator()(uint32_t idx, uint32_t) const
+    {
+        if (list) {
+            const uint32_t i = atomicAdd(list, 1u);
+            if (i < cap) list[2 + i] = idx;
+        } else {
+            atomicOr(tab + (idx >> 5), 1u << (idx & 31));
+        }
+    }
 };
 template <bool SIGNED>
 struct SpillCounter {  // saturating CAS add (countminsketch.py:280-284,312-316 / countingbloom.py:149-153)
@@ -379,7 +391,10 @@ struct SpillBloomFlag {  // PayTileTag probe of an overflowing segment: test it 
                      // re-checked key by key at the finish: exact)
     __device__ __forceinline__ void operator()(uint32_t idx, uint32_t tile) const
     {
-        if (defer || ((tab[idx >> 5] >> (idx & 31)) & 1u) == 0) tileflag[tile] = gen;
+        if (defer || ((tab[idx >> 5] >> (idx & 31)) & 1u) == 0) {
+            tileflag[tile] = gen;
+            tileflag[-1] = gen;  // "some tile of this round is flagged" (k_bloom_flag_resolve)
+        }
     }
 };
 
@@ -1459,10 +1474,22 @@ __device__ __forceinline__ void for_each_group_padded(const uint4 *buckets, cons
     });
 }
 
+// Store mode (first round of an insert into a table whose clear was deferred, psk_capi.hip psk_clear): the table's old contents are
+// dead, so the image is STORED -- every word of the slice, zeros included, no read -- and the workgroups also do the rest of k_clear's
+// work: the last one zeroes the table words behind the last slice, the first one the handle's counter block.  The probes pass 1 could
+// not bucket wait in spill (SpillBloomOr's list: [0] count, [1] workgroups done, [2 ..] bit indices); every workgroup ORs the entries
+// of its own slice into its image first (~10^3 entries per 10M keys), and the last workgroup to finish resets the two header words.
+constexpr uint32_t kBloomApplyCtrWords = 8;  // == PSK_CTR_COUNT (static_assert in psk_part_bloom_add.hip)
+struct BloomApplyStore {
+    uint32_t on = 0;
+    const uint32_t *spill = nullptr;
+    uint32_t spill_cap = 0;
+    long long *ctr = nullptr;
+};
 // Bloom insert: OR the slice's probes into an LDS image of the slice, then OR the image into the table.
 // dynamic LDS: slice image, 2^shift bits
 static __global__ __launch_bounds__(kApplyThreads) void k_bloom_apply(uint32_t *tab, uint64_t tab_words, PartGeom g,
-                                                               const uint32_t *segcnt, const uint4 *buckets)
+                                                               const uint32_t *segcnt, const uint4 *buckets, BloomApplyStore sm)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const uint32_t b = blockIdx.x;
@@ -1478,11 +1505,49 @@ static __global__ __launch_bounds__(kApplyThreads) void k_bloom_apply(uint32_t *
         if (nv > 2) { const uint32_t x = (uint32_t)(h >> 40) & 0xFFFFFu; atomicOr(&smem[x >> 5], 1u << (x & 31)); }
     };
     for_each_group(buckets, segcnt, g, b, make_uint4(0, 0, 0, 0), [&](const uint4 q) { half(q.x, q.y); half(q.z, q.w); });
+    if (sm.on) {
+        const uint32_t nsp = sm.spill[0] < sm.spill_cap ? sm.spill[0] : sm.spill_cap;
+        const uint32_t lmask = (1u << g.shift) - 1u;
+        for (uint32_t i = threadIdx.x; i < nsp; i += kApplyThreads) {
+            const uint32_t x = sm.spill[2 + i];
+            if ((x >> g.shift) == b) atomicOr(&smem[(x & lmask) >> 5], 1u << (x & 31));
+        }
+    }
     __syncthreads();
     // merge: this workgroup is the only writer of its slice
     const uint64_t w0 = (uint64_t)b * slice_words;
     const bool nt = (g.dbg & kGeomNtBit) != 0 && tab_words >= kNtTableWords;  // (see slice_piece)
     typedef unsigned int nt_u32x4 __attribute__((ext_vector_type(4)));
+    if (sm.on) {
+        for (uint32_t w = threadIdx.x * 4; w < slice_words; w += kApplyThreads * 4) {
+            const uint64_t gw = w0 + w;
+            const uint4 v = *reinterpret_cast<const uint4 *>(smem + w);
+            if (gw + 3 < tab_words) {
+                if (nt) {
+                    nt_u32x4 x;
+                    x.x = v.x; x.y = v.y; x.z = v.z; x.w = v.w;
+                    __builtin_nontemporal_store(x, reinterpret_cast<nt_u32x4 *>(tab + gw));
+                } else {
+                    *reinterpret_cast<uint4 *>(tab + gw) = v;
+                }
+            } else {
+                const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
+                for (uint32_t e = 0; e < 4; ++e)
+                    if (gw + e < tab_words) tab[gw + e] = vv[e];
+            }
+        }
+        if (b == gridDim.x - 1)
+            for (uint64_t gw = (uint64_t)gridDim.x * slice_words + threadIdx.x; gw < tab_words; gw += kApplyThreads) tab[gw] = 0;
+        if (b == 0 && threadIdx.x < kBloomApplyCtrWords) sm.ctr[threadIdx.x] = 0;
+        if (threadIdx.x == 0) {  // every lane of this workgroup has read the count (the barrier above): the last workgroup resets the list
+            uint32_t *hdr = const_cast<uint32_t *>(sm.spill);
+            if (atomicAdd(hdr + 1, 1u) == gridDim.x - 1) {
+                hdr[0] = 0;
+                hdr[1] = 0;
+            }
+        }
+        return;
+    }
     constexpr int kFold = 4;  // 16-byte pieces in flight per lane (one at a time was a chain of HBM round trips)
     for (uint32_t wb = threadIdx.x * 4; wb < slice_words; wb += kApplyThreads * 4 * kFold) {
         uint4 t[kFold], add[kFold];
@@ -1649,6 +1714,7 @@ static __global__ __launch_bounds__(kApplyThreads) void k_bloom_test_flag(const 
                 nmiss += (uint32_t)__builtin_popcount(clear);
                 const uint32_t ordinal = (q[d].y >> 30) | ((q[d].w >> 30) << 2);
                 tileflag[ordinal * g.nwg + wg[d]] = gen;
+                tileflag[-1] = gen;  // "some tile of this round is flagged" (k_bloom_flag_resolve)
             }
         }
     }, mycnt);
@@ -1667,7 +1733,8 @@ static __global__ __launch_bounds__(kApplyThreads) void k_bloom_test_flag(const 
 
 // Last step of the tile-flag lookup: pass 2 has answered every key "present"; the keys of a FLAGGED tile are checked one by one against
 // the table here (bloom.py:261-272: the direct kernel's loop) -- exact whatever the batch holds, next to nothing when no tile is flagged
-// (every workgroup reads its few flags and leaves).  Workgroup w owns the tiles w, w + gridDim.x, ...
+// (every workgroup reads tileflag[-1], which every flag store of the round also sets to `gen`, and leaves when no tile is flagged).
+// Workgroup w owns the tiles w, w + gridDim.x, ...
 // publish (last round of a call under the automatic scheme choice): workgroup 0 copies the call's miss tally to the pinned page the next
 // call's choice reads (what the one-thread k_lookup_publish launch does for the other schemes).
 constexpr int kResolveThreads = 1024;  // (a flagged tile is re-checked by ONE workgroup: two keys per thread, latency-bound gathers)
@@ -1687,6 +1754,7 @@ __global__ __launch_bounds__(kResolveThreads) void k_bloom_flag_resolve(Src src,
         pub.pin[3] = pub.pin[3] + 1;
         pub.tally[0] = 0;
     }
+    if (tileflag[-1] != gen) return;
     const uint64_t ntiles = (n + tile - 1) / tile;
     BloomCheck<POW2> op{tab, md, k, out};
     // 64 of my tiles at a time: lane l of every wave reads the flag of tile (t0 + l) * gridDim.x + blockIdx.x
