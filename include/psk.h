@@ -125,8 +125,9 @@ int psk_device_count(int *count);
  * "update_window_tile", "update_window_wide", "update_window_force_fail", "ragged_sort", "host_poll_us" (how long a tiny PSK_HOST call
  * polls its completion mailbox before it waits for the stream; 0 = never poll); read-only counters "cbf_ordered_replays",
  * "update_window_folds", "update_window_replays", "cms_small_weights_used", "cbf_lookup_shadow_hits".
- * The A/B switches of experiments that were measured and dropped (NOTES.md) exist only in the bench build (-DPSK_BENCH_KNOBS=1,
- * libpsk_hip_knobs.so); this library answers "unknown option" to them. */
+ * The bench build (-DPSK_BENCH_KNOBS=1, libpsk_hip_knobs.so) has one more option, "part_debug": the ablation / phase-profile bits of the
+ * measuring tools; this library answers "unknown option" to it.  The A/B switches of experiments that were measured and dropped are gone
+ * with their code (NOTES.md). */
 int psk_set_option(const char *name, int64_t value);
 int psk_get_option(const char *name, int64_t *value);
 /* Per-sketch options (round 4): "partition_min_keys", "cbf_lookup_shadow", "auto_combine", "update_window", "update_window_keys",

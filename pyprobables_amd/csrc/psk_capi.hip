@@ -614,9 +614,8 @@ int64_t g_part_cache_bytes = 240 << 20;  // bucket-buffer budget per round: the 
 int64_t g_part_two_level_slices = 2048;     // tables cut into more slices than this take the two-level path (0 = never)
 int64_t g_part_debug = 0;            // ablation bits for bench runs (see PartGeom::dbg); 0 in production
 __thread int64_t g_bloom_lookup = 2;
-int64_t g_lookup_run_lanes = 0, g_lookup_split = 1, g_part_tile_threads = 0, g_part_slice_bias = 0, g_part_wgs = 0, g_part_even_tiles = 1;
+int64_t g_part_tile_threads = 0, g_part_even_tiles = 1;
 int64_t g_lookup_half = 1;
-int64_t g_lookup_collect_threads = 0;   // pass 3 of the counter lookups: 0 = 512-thread workgroups up to 256 slices, 1024 beyond (psk_part_lookup.hpp); 512 / 1024 = forced
 int64_t g_remove_dryrun = 1;   // validated unit-weight CBF removes into big tables: optimistic decrement first (psk_nibble.hpp), option "remove_optimistic"
 __thread int64_t g_scratch_budget = 0;  // psk_set_option("scratch_budget_bytes"): cap on a handle's partition scratch (more, smaller rounds); 0 = none
 int64_t g_lookup_nibble = 1;   // CBF lookups into 2^25 .. 2^29 counters: 4-bit slice images (psk_nibble.hpp) from cells / 16 probes on; 2 = always; 0 = the 32-bit / 16-bit slices or direct
@@ -624,26 +623,10 @@ int64_t g_small_weights_used = 0;
 int64_t g_small_weights = 1;   // PayWeightSmall for weighted CountMinSketch adds (psk_sketch::wt)
 int64_t g_cbf_shadow_hits = 0;
 __thread int64_t g_cbf_shadow = 1;  // nibble-slice lookups keep their 4-bit images while the table is unchanged (psk_sketch::shadow; cells / 2 bytes)
-int64_t g_nib_nt = 1;   // nontemporal table loads in k_nib_gather (1 GiB lookups 710 -> 656 us per 10 M keys); the fold of k_nib_apply re-writes what it
-                        // reads and measured slower with them (795 -> 984 us): never there
 int64_t g_nib_min_lg_lookup = 23, g_nib_min_lg_update = 24;  // see nib_geometry (psk_host.hpp); measured crossovers: scripts/ab_nib_threshold.py
-int64_t g_nib_update_parts = 1;   // 1 = one workgroup per slice (default: two measured the same, 0.78-0.82 ms per 10 M adds either way), 2 = two, 0 = by slice size; see nib_update_lgparts
-int64_t g_nib_update_layout = 1;   // see psk_nibble.hpp (bench A/B)
 int64_t g_ragged_sort = 1;    // pass 1's per-tile length sort of ragged keys (A/B: 0 = batch order); option "ragged_sort"
-int64_t g_big_table_nt = 1;   // nontemporal table sweeps in the Bloom pass-2 kernels for tables of 128 MiB and more (BASELINE cfg 5); option "big_table_nt"
-int64_t g_window_shadow = 0;   // 1 = a successful window fold leaves the lookups' kept 4-bit images up to date (when they exist) instead of stale.  Measured on the
-                               // 1 GiB table (scripts/ab_window_shadow.py: rounds of 15 M window updates + a 10 M-key lookup): 2.99 vs 3.00 ms per round -- the
-                               // 0.1 ms the lookup saves is within the noise of the round and is partly paid by the fold's 128 MiB of image stores: off
-int64_t g_window_shadow_writes = 0;  // folds that did (tests)
 int64_t g_window_wide = 1;    // update windows on tables of few slices: the fold with five probe groups per lane and phase and byte-wide group counts (0: three, nibbles)
 int64_t g_window_tile = 0;    // keys per pass-1 tile of an update window: 0 = rule (4096 for tables of many slices), 2048 / 4096 forced; option "update_window_tile"
-int64_t g_window_image = 4;   // update windows' fold: 4 = nibble images, one workgroup per 2^18-counter slice; 8 = byte images, two per slice (round 4 A/B)
-int64_t g_window_nt = 1;   // nontemporal table loads / stores in the update windows' fold (k_win_fold); option "update_window_nt"
-int64_t g_nib_gather_pipe = 0;   // 1 = k_nib_gather_pipe (psk_nibble_pipe.hpp: the next slice's table load under this slice's probe walk) when no kept images exist.
-                                 // Measured on MI355X: 260 vs 257 us per 10 M keys -- no gain (the register budget allows one 4-piece load step in flight, which
-                                 // cannot keep the table stream busy; deeper variants spill: 366 us), so it stays off: k_nib_gather
-int64_t g_nib_update_pipe = 1;   // 1 = k_nib_apply_pipe (psk_nibble_pipe.hpp: persistent workgroups, fold of slice s under the probes of slice s + 1; nontemporal
-                                 // table accesses: 551 -> 514 us per 10 M adds), 3 = the same with plain accesses (A/B), 0 = k_nib_apply
 int64_t g_update_nibble = 1;   // CBF unit-weight adds / decrements into 2^26 .. 2^29 counters: 4-bit delta images, one level; 0 = two-level 32-bit path
 int64_t g_part_bins = 1;   // pass 1 through fixed-capacity bins wherever eligible (psk_part_bins.hpp); option "pass1_bins"
 int64_t g_part_dense_groups = 40;   // pass 2: segments of fewer groups (mean) are walked end to end (for_each_batch_at); 0 = never
@@ -652,7 +635,7 @@ extern PSK_HIDDEN int64_t g_merge_single_rank;  // psk_merge.hip
 // ---- process-wide options: ONE table.  Three classes (include/psk.h lists the first by name):
 //   supported   tunables of the shipped library a caller may have a reason to touch;
 //   threshold   where the engine switches between its kernel families, and test hooks -- tests steer small inputs onto the big-table paths with them;
-//   knob        A/B switches of experiments that were measured and dropped: compiled in only with -DPSK_BENCH_KNOBS=1
+//   knob        "part_debug" alone, the ablation / phase-profile bits of the measuring tools: compiled in only with -DPSK_BENCH_KNOBS=1
 //               (python -m pyprobables_amd.build --knobs -> libpsk_hip_knobs.so), the shipped library answers "unknown option";
 //   read-only   counters tests read back.
 // (the per-sketch options -- kHoNames -- are handled in front of the table: their process defaults live in d_opt)
@@ -698,25 +681,8 @@ const OptDesc kOptions[] = {
     {"update_window_replays", &g_window_replays, kOptReadOnly, kAny},
     {"cms_small_weights_used", &g_small_weights_used, kOptReadOnly, kAny},
     {"cbf_lookup_shadow_hits", &g_cbf_shadow_hits, kOptReadOnly, kAny},
-    // retired experiments (bench builds only)
+    // measuring tools (bench builds only)
     {"part_debug", &g_part_debug, kOptKnob, kAny},
-    {"combine_scatter", &g_combine_scatter, kOptKnob, kAny},
-    {"combine_fused_flush", &g_fused_flush, kOptKnob, kAny},
-    {"lookup_run_lanes", &g_lookup_run_lanes, kOptKnob, kAny},
-    {"lookup_split", &g_lookup_split, kOptKnob, kAny},
-    {"lookup_collect_threads", &g_lookup_collect_threads, kOptKnob, kAny},
-    {"slice_bias", &g_part_slice_bias, kOptKnob, kAny},
-    {"scatter_workgroups", &g_part_wgs, kOptKnob, kAny},
-    {"nibble_update_layout", &g_nib_update_layout, kOptKnob, kAny},
-    {"nibble_update_parts", &g_nib_update_parts, kOptKnob, kAny},
-    {"nibble_update_pipe", &g_nib_update_pipe, kOptKnob, kAny},
-    {"nibble_lookup_pipe", &g_nib_gather_pipe, kOptKnob, kAny},
-    {"nibble_nt_loads", &g_nib_nt, kOptKnob, kAny},
-    {"update_window_nt", &g_window_nt, kOptKnob, kAny},
-    {"update_window_image", &g_window_image, kOptKnob, kAny},
-    {"update_window_shadow", &g_window_shadow, kOptKnob, kAny},
-    {"update_window_shadow_writes", &g_window_shadow_writes, kOptKnob, kAny},
-    {"big_table_nt", &g_big_table_nt, kOptKnob, kAny},
 };
 const OptDesc *opt_find(const char *name)
 {
@@ -1066,10 +1032,6 @@ static int cbf_apply_device(psk_sketch *s, const Batch &b, const uint32_t *w, bo
 }
 
 // ---- write-combined updates as scattered probes (psk_sketch::scat, psk_nibble.hpp)
-int64_t g_fused_flush = 0;             // flush of both write-combined key lists as two pass 1s + ONE fold (adds, then decrements, per slice): measured
-                                       // SLOWER on BASELINE cfg 4 (4.50 vs 3.80 ms per step: one workgroup per slice streams both lists and folds twice
-                                       // back to back, nothing overlaps) -- off; option "combine_fused_flush"
-int64_t g_combine_scatter = 0;         // psk_cbf_update_combined: 1 = unit-weight batches wait as scattered probes instead of key lists (see there)
 __thread int64_t g_auto_combine = 1;            // psk_cbf_add: small unit-weight batches into big tables wait as scattered probes (adds commute: exact)
 int64_t g_auto_combine_keys = 1 << 24; // keys per list in that mode (~0.8 GB of segments for k = 7, allocated on first use)
 
@@ -1123,23 +1085,21 @@ static int scat_flush(psk_sketch *s, hipStream_t st)
     PartGeom g = s->scat.g;
     const uint64_t per_seg = (uint64_t)g.nbuckets * g.nwg * 6;
     g.dense = ((na > nr ? na : nr) * s->k / per_seg) < (uint64_t)g_part_dense_groups ? 1u : 0u;
-    const uint32_t lgp = nib_update_lgparts(g);
-    const size_t lds = (size_t)1 << (g.shift - 1 - lgp);
+    const size_t lds = (size_t)1 << (g.shift - 1);
     unsigned long long *sat = (unsigned long long *)(s->ctr + PSK_CTR_SATURATED);
     const bool pass_a = na * s->k >= s->m / 8, pass_r = nr * s->k >= s->m / 8;
     auto launch = [&](auto kern, const psk_sketch::ScatList *la, const psk_sketch::ScatList *lb, uint32_t direct) {
         PSK_TRY(set_dyn_lds(kern, lds));
-        hipLaunchKernelGGL(kern, dim3(g.nbuckets << lgp), dim3(kApplyThreads), lds, st, (uint32_t *)s->table, s->m, g, (const uint32_t *)la->cnt.p, (const uint4 *)la->part.p,
-                           (const uint32_t *)(lb ? lb->cnt.p : nullptr), (const uint4 *)(lb ? lb->part.p : nullptr), sat, direct | (lgp << 8), (uint32_t *)nullptr, g);
+        hipLaunchKernelGGL(kern, dim3(g.nbuckets), dim3(kApplyThreads), lds, st, (uint32_t *)s->table, s->m, g, (const uint32_t *)la->cnt.p, (const uint4 *)la->part.p,
+                           (const uint32_t *)(lb ? lb->cnt.p : nullptr), (const uint4 *)(lb ? lb->part.p : nullptr), sat, direct, g);
         HIP_TRY(hipGetLastError());
         return (int)PSK_OK;
     };
-    const bool blocks = g_nib_update_layout != 0;
     if (na && nr && pass_a && pass_r) {
-        PSK_TRY(blocks ? launch(k_nib_apply<2, true>, &s->scat.add, &s->scat.rem, 0u) : launch(k_nib_apply<2, false>, &s->scat.add, &s->scat.rem, 0u));
+        PSK_TRY(launch(k_nib_apply<2>, &s->scat.add, &s->scat.rem, 0u));
     } else {
-        if (na) PSK_TRY(blocks ? launch(k_nib_apply<0, true>, &s->scat.add, nullptr, pass_a ? 0u : 1u) : launch(k_nib_apply<0, false>, &s->scat.add, nullptr, pass_a ? 0u : 1u));
-        if (nr) PSK_TRY(blocks ? launch(k_nib_apply<1, true>, &s->scat.rem, nullptr, pass_r ? 0u : 1u) : launch(k_nib_apply<1, false>, &s->scat.rem, nullptr, pass_r ? 0u : 1u));
+        if (na) PSK_TRY(launch(k_nib_apply<0>, &s->scat.add, nullptr, pass_a ? 0u : 1u));
+        if (nr) PSK_TRY(launch(k_nib_apply<1>, &s->scat.rem, nullptr, pass_r ? 0u : 1u));
     }
     return scat_zero(s, na != 0, nr != 0, st);
 }
@@ -1422,35 +1382,6 @@ int flush_combined(psk_sketch *s, hipStream_t st)
         l.unit = true;
         return cbf_apply_device(s, b, unit ? nullptr : (const uint32_t *)l.w.p, pass == 1, st);
     };
-    // Both key lists due, unit weights, big table: scatter both (two bucket buffers), then ONE fold -- adds, then decrements -- per slice
-    // (k_nib_apply<2>): the slice a workgroup has just written is still on-die when it reads it back for the decrements.
-    // (only when no OTHER mechanism holds adds of this window: they would have to land before these removes)
-    if (s->comb.add.n && s->comb.rem.n && s->comb.add.unit && s->comb.rem.unit && g_fused_flush != 0 && s->comb.add.n * s->k >= s->m / 8 &&
-        s->comb.rem.n * s->k >= s->m / 8 && s->comb.badd.n() == 0 && !(s->scat.ready && s->scat.add.n != 0)) {
-        Batch ba{PSK_KEYS_FIXED, s->comb.add.keys.p, nullptr, s->comb.add.n, s->comb.key_len};
-        Batch br{PSK_KEYS_FIXED, s->comb.rem.keys.p, nullptr, s->comb.rem.n, s->comb.key_len};
-        PartGeom ga, gr;
-        bool oka = false, okr = false;
-        PSK_TRY(cbf_nib_scatter(s, ba, 0, 0, &ga, st, &oka));
-        if (oka) PSK_TRY(cbf_nib_scatter(s, br, 1, 1, &gr, st, &okr));
-        if (oka && okr) {
-            const uint64_t na = s->comb.add.n, nr = s->comb.rem.n;
-            s->comb.add.n = s->comb.rem.n = 0;
-            PSK_TRY(account_weights(s, (const uint32_t *)nullptr, na, PSK_CTR_ADDED, (long long)s->k, st, true));
-            PSK_TRY(account_weights(s, (const uint32_t *)nullptr, nr, PSK_CTR_REMOVED, (long long)s->k, st, false));
-            const uint32_t lgp = nib_update_lgparts(ga);
-            const size_t lds = (size_t)1 << (ga.shift - 1 - lgp);
-            auto launch2 = [&](auto kern) {
-                PSK_TRY(set_dyn_lds(kern, lds));
-                hipLaunchKernelGGL(kern, dim3(ga.nbuckets << lgp), dim3(kApplyThreads), lds, st, (uint32_t *)s->table, s->m, ga, (const uint32_t *)s->s_cnt.p, (const uint4 *)s->s_part.p,
-                                   (const uint32_t *)s->s_cnt2.p, (const uint4 *)s->s_part2.p, (unsigned long long *)(s->ctr + PSK_CTR_SATURATED), lgp << 8, (uint32_t *)nullptr, gr);
-                HIP_TRY(hipGetLastError());
-                return (int)PSK_OK;
-            };
-            PSK_TRY(g_nib_update_layout ? launch2(k_nib_apply<2, true>) : launch2(k_nib_apply<2, false>));
-        }
-        // (oka && !okr: the adds sit scattered in s_part but nothing was applied -- the lists are untouched, the general path below redoes them)
-    }
     PSK_TRY(key_list(0));
     PSK_TRY(borrowed_flush(s, s->comb.badd, false, st));
     if (scat_pending && (s->comb.rem.n != 0 || s->comb.brem.n() != 0) && s->scat.add.n != 0) {  // key-list removes wait: the scattered adds must land before them
@@ -1498,20 +1429,6 @@ extern "C" int psk_cbf_update_combined(psk_sketch *s, int layout, const void *da
             return comb_appended(s, st);  // (a flush on another stream waits for this one: the keys may still be in the making on it)
         }
         where = PSK_DEVICE;  // anything else is copied as usual
-    }
-    // Scattered probes instead of key lists (option "combine_scatter", off): pass 1 per batch saves the key copy and the second read
-    // of the keys, but measured on BASELINE cfg 4 (99 batches of 0.5-1 M keys) it costs more than it saves -- a 1 M-key pass 1 runs
-    // two tiles per workgroup and pays its fixed costs (1024 cursors read and written per workgroup, pipeline fill) every time:
-    // 45 us per batch against 7 us for the copy plus 21 us per 1 M keys of a 50 M-key pass 1; the step took 6.7 ms instead of 3.9.
-    if (!weights && cap && g_combine_scatter != 0) {
-        Batch b;
-        PSK_TRY(stage_batch(s->s_keys, s->s_offs, layout, data, offsets, n, key_len, where, st, &b));
-        bool taken = false;
-        PSK_TRY(scat_append(s, b, remove != 0, cap, st, &taken));
-        if (taken) {
-            PSK_TRY(account_weights(s, (const uint32_t *)nullptr, n, remove ? PSK_CTR_REMOVED : PSK_CTR_ADDED, (long long)s->k, st, !remove));
-            return finish(where, nullptr, st);
-        }
     }
     const bool combinable = layout == PSK_KEYS_FIXED && key_len > 0 && data && n < cap;
     if (!combinable || (s->comb.key_len && s->comb.key_len != key_len) || (s->comb.cap && s->comb.cap != cap)) {

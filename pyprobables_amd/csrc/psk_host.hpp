@@ -245,26 +245,18 @@ static inline int grid_for_keys(uint64_t n)  // direct kernels: 256 CUs x 16 blo
 extern PSK_HIDDEN __thread int64_t g_part_min_keys;
 extern PSK_HIDDEN int64_t g_part_mode, g_part_max_keys, g_part_cache_bytes, g_part_two_level_slices, g_part_debug;
 extern PSK_HIDDEN __thread int64_t g_bloom_lookup;      // Bloom lookups: 0 keyed probes + miss stores, 1 return trip (psk_lookup.hpp), 2 (default) by the observed miss rate
-extern PSK_HIDDEN int64_t g_part_slice_bias;     // bench knob: added to log2(cells per slice)
 extern PSK_HIDDEN int64_t g_part_tile_threads;   // pass 1 workgroup shape for k <= 8: 0 = auto (launch_scatter), 512 / 1024 = forced
 extern PSK_HIDDEN int64_t g_part_even_tiles;     // 1 (default): pass 1 evens the tile size out over the workgroups
 extern PSK_HIDDEN int64_t g_lookup_half;           // 1 (default): counter lookups into 2^26 .. 2^27 counters use 2^16-counter slices of 16-bit values
 extern PSK_HIDDEN int64_t g_small_weights;     // weighted CMS adds: 0 never the compact probe format, 1 by the hint, 2 always (tests)
 extern PSK_HIDDEN __thread int64_t g_cbf_shadow;         // keep the nibble-slice lookup's images of an unchanged table
-extern PSK_HIDDEN int64_t g_nib_nt;             // nontemporal table loads in the nibble-slice kernels (bench A/B)
-extern PSK_HIDDEN int64_t g_nib_update_layout;  // delta-image layout of k_nib_apply: 0 pieces, 1 blocks (psk_nibble.hpp)
 extern PSK_HIDDEN int64_t g_lookup_nibble, g_update_nibble;  // CBF tables beyond one level of 32-bit slices: 4-bit slice images (psk_nibble.hpp)
 extern PSK_HIDDEN int64_t g_part_dense_groups;   // pass 2 walks a wave's segments end to end when a segment holds fewer groups than this on average (0 = never)
 extern PSK_HIDDEN int64_t g_ragged_sort;         // option "ragged_sort": pass 1 hands keys of different lengths to its lanes in order of length (psk_partition.hpp sort_tile)
-extern PSK_HIDDEN int64_t g_big_table_nt;        // option "big_table_nt": nontemporal sweeps of Bloom tables of 128 MiB and more (psk_partition.hpp slice_piece)
-extern PSK_HIDDEN int64_t g_part_wgs;            // bench knob: pass 1 workgroups (0 = auto: one or two per CU)
-extern PSK_HIDDEN int64_t g_lookup_split;        // bench knob: 0 = never share a slice between two pass-2 workgroups
-extern PSK_HIDDEN int64_t g_lookup_collect_threads;  // pass 3 of the counter lookups: 1024 (two tiles in flight per CU) or 512 (four)
-extern PSK_HIDDEN int64_t g_lookup_run_lanes;  // bench knob of the counter lookups (lanes per run in pass 3; 0 = auto)
 
 // slices of a table of `cells` cells; max_shift = log2(cells one LDS slice may hold)
 // target_lg: aim at 2^target_lg .. 2^(target_lg+1)-1 slices.  8 (one slice per CU or more) for the Bloom tables; the counter
-// tables take 7: measured on MI355X (scripts/ab_slices.py, CMS 2^20 x 5) 160 slices of 2^15 counters beat 320 of 2^14 --
+// tables take 7: measured on MI355X (NOTES.md §3.2, CMS 2^20 x 5) 160 slices of 2^15 counters beat 320 of 2^14 --
 // pass 1 sorts into half as many bins with runs twice as long (weighted add 211 -> 193 us, lookups 314 -> 302 us), which
 // outweighs pass 2 running on 160 of the 256 CUs.
 static inline bool part_slices(uint64_t cells, uint32_t max_shift, uint32_t min_shift, PartGeom *g,
@@ -272,14 +264,14 @@ static inline bool part_slices(uint64_t cells, uint32_t max_shift, uint32_t min_
 {
     if (cells >= (1ULL << 32) || cells < (1ULL << 16)) return false;  // cell index 0xFFFFFFFF is the pad marker
     const uint32_t lg = 63 - __builtin_clzll(cells);  // floor(log2 cells)
-    int shift = (int)lg - target_lg + (int)g_part_slice_bias;  // (bias: bench knob)
+    int shift = (int)lg - target_lg;
     if (shift > (int)max_shift) shift = max_shift;
     if (shift < (int)min_shift) shift = min_shift;
     const uint64_t B = (cells + (1ULL << shift) - 1) >> shift;
     if (B > max_buckets) return false;
     g->nbuckets = (uint32_t)B;
     g->shift = (uint32_t)shift;
-    g->dbg = (uint32_t)g_part_debug | (g_big_table_nt != 0 ? kGeomNtBit : 0u) | (g_ragged_sort == 0 ? kGeomNoSortBit : 0u);
+    g->dbg = (uint32_t)g_part_debug | (g_ragged_sort == 0 ? kGeomNoSortBit : 0u);
     g->split = g->split_idx = 0;
     g->dense = 0;
     g->append = 0;
@@ -294,15 +286,6 @@ static inline bool nib_geometry(uint64_t cells, bool update, PartGeom *g)
 {
     if (update ? cells <= (1ULL << g_nib_min_lg_update) : cells < (1ULL << g_nib_min_lg_lookup)) return false;
     return part_slices(cells, kNibShift, 15, g, kPartMaxBuckets, 8);
-}
-
-// workgroups per slice of k_nib_apply (log2): 2 for the 2^18-counter slices (two 64 KiB delta images per CU: one streams probes while the
-// other folds -- psk_nibble.hpp nib_apply_list); option "nibble_update_parts": 0 = this rule, 1 / 2 = forced (bench A/B)
-extern PSK_HIDDEN int64_t g_nib_update_parts;
-static inline uint32_t nib_update_lgparts(const PartGeom &g)
-{
-    if (g_nib_update_parts > 0) return g_nib_update_parts >= 2 && g.shift >= 16 ? 1u : 0u;
-    return g.shift >= 18 ? 1u : 0u;
 }
 
 // A 4-bit DELTA image holds at most 15 hits per counter and round; a round that brings more than ~2.5 probes per counter on average
@@ -384,6 +367,9 @@ struct BinsPlan {
 template <int KT>
 static bool bins_plan(const PartGeom *g, BinsPlan *p)
 {
+    // (every geometry comes from part_slices, which gives at least 32 slices for any table it accepts -- the 4-bit geometry at 2^20 counters,
+    // the least nibble_min_lg_* allows; the Bloom and counter callers 128 or more --, so the lanes k_part_bins lets share a slice, at most
+    // kBinThreads / 64 of them, are neighbours inside one wave)
     if (g_part_bins == 0 || g->nbuckets > (uint32_t)kBinThreads * kBinSlicesPerLane || g->nbuckets < 2) return false;
     constexpr double kSigmas = 3.5;  // bin capacity = mean + 3.5 sigma of a tile's load: ~1e-3 of the bins of a tile fill up (2.8 measured the same)
     const uint32_t kk = g->k < (uint32_t)KT ? g->k : (uint32_t)KT;
@@ -415,7 +401,6 @@ static int launch_scatter_bins(psk_sketch *s, const Src &src, const IdxFn &idxfn
     // (32-bit key indices inside the kernel: n < 2^31, the caller checked; the prefetch of the tile behind the last one stays below 2^32)
     uint64_t nwg = 256ULL * bp.per_cu;
     if (want_wgs) nwg = want_wgs;
-    if (g_part_wgs > 0) nwg = (uint64_t)g_part_wgs;
     if (nwg > 64u * kApplyWaves) nwg = 64u * kApplyWaves;  // pass 2: a wave walks at most one segment per lane (for_each_batch_at)
     if (nwg > ntiles) nwg = ntiles;
     if (nwg == 0) nwg = 1;
@@ -489,7 +474,6 @@ static int launch_scatter_nt(psk_sketch *s, const Src &src, const IdxFn &idxfn, 
     if (kBenchKnobs && (g->dbg & 8)) per_cu = 1;  // ablation: one workgroup per CU
     uint64_t nwg = 256 * per_cu;
     if (want_wgs) nwg = want_wgs;  // caller's choice (keyed lookups into big tables: twice the keys per round)
-    if (g_part_wgs > 0) nwg = (uint64_t)g_part_wgs;
     if (nwg > 64u * kApplyWaves) nwg = 64u * kApplyWaves;  // pass 2: a wave walks at most one segment per lane (for_each_batch_at)
     if (nwg > ntiles) nwg = ntiles;
     const uint64_t tiles_per_wg = (ntiles + nwg - 1) / nwg;
@@ -562,7 +546,6 @@ static uint64_t scatter_round_cap(const PartGeom *g, uint32_t want_wgs, uint32_t
         if (bins_plan<KT>(g, &bp)) {
             uint64_t nwg = 256ULL * bp.per_cu;
             if (want_wgs) nwg = want_wgs;
-            if (g_part_wgs > 0) nwg = (uint64_t)g_part_wgs;
             if (nwg > 64u * kApplyWaves) nwg = 64u * kApplyWaves;
             return nwg * max_tiles * bp.tile;
         }
@@ -576,7 +559,6 @@ static uint64_t scatter_round_cap(const PartGeom *g, uint32_t want_wgs, uint32_t
     uint64_t nwg = 256 * (uint64_t)(big ? 1 : (lds > kScatterLdsTwoPerCu ? 1 : 2));
     if (kBenchKnobs && (g->dbg & 8)) nwg = 256;
     if (want_wgs) nwg = want_wgs;
-    if (g_part_wgs > 0) nwg = (uint64_t)g_part_wgs;
     if (nwg > 64u * kApplyWaves) nwg = 64u * kApplyWaves;
     return nwg * max_tiles * tile;
 }
@@ -814,8 +796,6 @@ PSK_DECLARE_VARIANTS(int, cbf_scat_append, (psk_sketch *s, const Batch &b, int n
 // unit-weight add (neg = 0) / unchecked decrement (neg = 1) of `n` borrowed 16-byte keys (device tables base[nb], start[nb + 1]) through the
 // nibble path; *done = false: table not eligible (nothing launched)
 PSK_DECLARE_VARIANTS(int, cbf_unit_multi_partitioned, (psk_sketch *s, const void *const *base_dev, const uint64_t *start_dev, uint32_t nb, uint64_t n, int neg, hipStream_t st, bool *done))
-// pass 1 alone of a unit-weight batch into the handle's first / second bucket buffer (fused flush of the write-combined lists)
-PSK_DECLARE_VARIANTS(int, cbf_nib_scatter, (psk_sketch *s, const Batch &b, int neg, int second, PartGeom *g_out, hipStream_t st, bool *done))
 // validated unit-weight remove, fast path: pass 1 + the optimistic decrement (flag in s_flag); flag up: _undo adds the probe groups back
 PSK_DECLARE_VARIANTS(int, cbf_remove_fast_begin, (psk_sketch *s, const Batch &b, hipStream_t st, bool *launched))
 PSK_DECLARE_VARIANTS(int, cbf_remove_fast_undo, (psk_sketch *s, hipStream_t st))
@@ -832,4 +812,4 @@ extern PSK_HIDDEN int64_t g_cbf_ordered_replays;
 extern PSK_HIDDEN int64_t g_window_folds, g_window_replays, g_window_force_fail;
 extern PSK_HIDDEN int64_t g_remove_dryrun;
 extern PSK_HIDDEN __thread int64_t g_auto_combine;
-extern PSK_HIDDEN int64_t g_auto_combine_keys, g_combine_keys, g_combine_scatter, g_fused_flush;
+extern PSK_HIDDEN int64_t g_auto_combine_keys, g_combine_keys;

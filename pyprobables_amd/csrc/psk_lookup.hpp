@@ -193,7 +193,7 @@ struct QueryCbfMin {   // countingbloom.py:166-174
 };
 
 // dynamic LDS: runinfo[B] (uint2) | stage[stage_cap] (values in the tile's sorted order) | fmt[B] bytes
-// kCollectThreads: 1024 = two workgroups (tiles in flight) per CU, 512 = four (round 3 A/B: option "lookup_collect_threads")
+// kCollectThreads: 1024 = two workgroups (tiles in flight) per CU, 512 = four (the host's rule: psk_part_lookup.hpp; NOTES.md §3.3)
 template <class Query, int KT, int kCollectThreads>
 __global__ __launch_bounds__(kCollectThreads) void k_lookup_collect(Query query, PartGeom g, uint64_t n, const uint32_t *perm, const uint2 *runinfo,
                                                                     const uint32_t *vals, const uint8_t *fmt, uint32_t stage_cap, uint32_t run_lanes,
@@ -339,7 +339,7 @@ static __global__ __launch_bounds__(kApplyThreads) void k_bloom_gather(const uin
     const uint32_t slice_words = 1u << (g.shift - 5);
     const uint64_t w0 = (uint64_t)b * slice_words;
     const uint32_t mycnt = lane_segment_count(segcnt, g, b);
-    load_slice(smem, tab, tab_words, w0, slice_words, (g.dbg & kGeomNtBit) != 0);
+    load_slice(smem, tab, tab_words, w0, slice_words);
     __syncthreads();
     // (8 groups in flight per lane: 48 LDS words + the 8 groups stay inside the 128 VGPRs of a 1024-thread workgroup; with 12
     // the kernel spilled and ran 3x slower)

@@ -59,8 +59,8 @@ __device__ __forceinline__ uint4 nib_load_piece(const uint32_t *tab, uint64_t ta
     return t;
 }
 
-// loads slice b of the table into the LDS nibble image (2^(shift-3) words)
-__device__ __forceinline__ void nib_load_slice(uint32_t *smem, const uint32_t *tab, uint64_t tab_cells, uint32_t shift, uint32_t b, bool nt)
+// loads slice b of the table into the LDS nibble image (2^(shift-3) words), nontemporal loads
+__device__ __forceinline__ void nib_load_slice(uint32_t *smem, const uint32_t *tab, uint64_t tab_cells, uint32_t shift, uint32_t b)
 {
     const uint32_t pieces = 1u << (shift - 2);
     const uint64_t c0 = (uint64_t)b << shift;
@@ -71,7 +71,7 @@ __device__ __forceinline__ void nib_load_slice(uint32_t *smem, const uint32_t *t
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t pc = p0 + (uint32_t)u * kApplyThreads;
-            t[u] = pc < pieces ? nib_load_piece(tab, tab_cells, c0 + 4ULL * pc, nt) : make_uint4(0, 0, 0, 0);
+            t[u] = pc < pieces ? nib_load_piece(tab, tab_cells, c0 + 4ULL * pc, true) : make_uint4(0, 0, 0, 0);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -83,9 +83,9 @@ __device__ __forceinline__ void nib_load_slice(uint32_t *smem, const uint32_t *t
 
 // shadow_in: the slice images as an earlier launch left them (psk_sketch::shadow: a linear 4-bit copy of the table, valid while the
 // table is unchanged) -- 1/8 of the bytes; shadow_out: leave them behind for the next lookup.  Both null: build and forget.
+// The table is loaded with nontemporal loads (1 GiB lookups: 710 -> 656 us per 10 M keys).
 static __global__ __launch_bounds__(kApplyThreads) void k_nib_gather(const uint32_t *tab, uint64_t tab_cells, PartGeom g, const uint32_t *segcnt,
-                                                                     const uint4 *buckets, uint32_t *vals, uint32_t nt, const uint32_t *shadow_in,
-                                                                     uint32_t *shadow_out)
+                                                                     const uint4 *buckets, uint32_t *vals, const uint32_t *shadow_in, uint32_t *shadow_out)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const uint32_t b = blockIdx.x;
@@ -109,7 +109,7 @@ static __global__ __launch_bounds__(kApplyThreads) void k_nib_gather(const uint3
             }
         }
     } else {
-        nib_load_slice(smem, tab, tab_cells, g.shift, b, nt != 0);
+        nib_load_slice(smem, tab, tab_cells, g.shift, b);
     }
     __syncthreads();
     if (shadow_out) {  // (the stores drain under the probe stream below)
@@ -247,9 +247,9 @@ __global__ __launch_bounds__(kBlock) void k_cbf_recheck15(const uint32_t *amb, S
 // meets in practice -- every key present -- a much cheaper test suffices: with R[c] = how often the batch's probes hit counter c,
 //      T[c] >= R[c] for every counter c (none of them frozen)   ==>   every key of the batch is removed, in any order
 // (whatever was removed before key X, each of X's counters still holds T[c] - (R[c] - 1) >= 1 just before X's own decrement, so
-// its min is >= 1 and to_remove = num_els = 1), and the result is T - R.  The fold of k_nib_apply sees T[c] and R[c] side by
-// side, so it checks the condition WHILE it decrements (OPT = 1: wrapping subtraction, a device flag for t < d or a frozen
-// counter).  Flag clear: done -- one pass 1 and one pass over the table.  Flag up: the same probe groups are added back (OPT = 2:
+// its min is >= 1 and to_remove = num_els = 1), and the result is T - R.  The fold of k_nib_apply_pipe (psk_nibble_pipe.hpp) sees
+// T[c] and R[c] side by side, so it checks the condition WHILE it decrements (OPT = 1: wrapping subtraction, a device flag for t < d
+// or a frozen counter).  Flag clear: done -- one pass 1 and one pass over the table.  Flag up: the same probe groups are added back (OPT = 2:
 // wrapping addition, the exact inverse) and the exact path (lookup, amounts, masked decrement) takes the batch.  A dry run that
 // only checked (a saturating image of the table + one returning ds_sub per probe) measured 403 us per 10 M keys on top of the
 // 509 us decrement; the optimistic form has no extra pass at all.
@@ -261,93 +261,64 @@ __global__ __launch_bounds__(kBlock) void k_cbf_recheck15(const uint32_t *amb, S
 // neighbour: every hit is a RETURNING ds_add whose old nibble tells (15 -> overflow); the workgroup then drops its image and
 // applies its probe groups with exact saturating atomics on the table -- the slice is its alone -- so the result is exact for
 // any batch (duplicate-heavy ones just run that slice at the direct rate).
-// The DELTA image of the update kernel comes in two layouts (bench A/B, option "nibble_update_layout"): 0 = as above (one 16-bit
-// half per 16-byte piece); 1 = blocks of 8192 counters, word (block, t) = the pieces t and 1024 + t of the block, so that a lane
-// folds two pieces 16 KiB apart per image word.
-template <bool BLOCKS>
-__device__ __forceinline__ uint32_t dlt_word(uint32_t cell) { return BLOCKS ? (((cell >> 13) << 10) | ((cell >> 2) & 1023u)) : (cell >> 3); }
-template <bool BLOCKS>
-__device__ __forceinline__ uint32_t dlt_bit(uint32_t cell) { return BLOCKS ? (((cell >> 8) & 16u) | ((cell & 3u) << 2)) : ((cell & 7u) << 2); }
+// The DELTA image: blocks of 8192 counters, word (block, t) = the pieces t and 1024 + t of the block, so that a lane folds two pieces
+// 16 KiB apart per image word.
+__device__ __forceinline__ uint32_t dlt_word(uint32_t cell) { return ((cell >> 13) << 10) | ((cell >> 2) & 1023u); }
+__device__ __forceinline__ uint32_t dlt_bit(uint32_t cell) { return ((cell >> 8) & 16u) | ((cell & 3u) << 2); }
 
-// one list (segcnt, buckets) into slice b; `direct`: skip the image and apply every probe with an atomic on the table (few probes:
-// a pass over the whole slice would cost more)
-// OPT 0: the reference's saturating add / checked decrement; 1 (NEG): optimistic decrement, see above; 2 (!NEG): its inverse
-// Round 4: a slice may be shared by 2^lgp workgroups (PARTS): workgroup h of a slice owns the counters [h << pshift, (h + 1) << pshift), pshift =
-// shift - lgp -- it streams ALL probe groups of the slice, applies those of its part and folds its part of the table.  With 2^17-counter
-// parts the delta image is 64 KiB, two workgroups fit one CU, and one of them streams probes (LDS-atomic bound) while the other folds
-// (HBM bound): the pass over a 1 GiB table was 3.0-3.7 TB/s with one 128 KiB workgroup per CU, whose phases only follow each other; the
-// probe groups are a tenth of the bytes, reading them twice costs little.
-constexpr int kNibDepth = 6;  // probe groups in flight per lane in k_nib_apply (two workgroups per CU share the latency hiding)
-template <bool NEG, bool BLOCKS, int OPT = 0>
+// one list (segcnt, buckets) into slice b: the reference's saturating add / checked decrement; `direct`: skip the image and apply every
+// probe with an atomic on the table (few probes: a pass over the whole slice would cost more)
+constexpr int kNibDepth = 6;  // probe groups in flight per lane in k_nib_apply
+template <bool NEG>
 __device__ __forceinline__ void nib_apply_list(uint32_t *smem, uint32_t *carried, uint32_t *tab, uint64_t tab_cells, const PartGeom &g, const uint32_t *segcnt,
-                                               const uint4 *buckets, unsigned long long *sat_ctr, uint32_t b, bool direct, bool nt, uint32_t *flag = nullptr,
-                                               uint32_t lgp = 0, uint32_t h = 0)
+                                               const uint4 *buckets, unsigned long long *sat_ctr, uint32_t b, bool direct)
 {
-    uint32_t bad = 0;
-    const uint32_t pshift = g.shift - lgp, pmask = (1u << pshift) - 1;
-    const uint32_t pieces = 1u << (pshift - 2);
-    const uint64_t c0 = ((uint64_t)b << g.shift) + ((uint64_t)h << pshift);
+    const uint64_t c0 = (uint64_t)b << g.shift;
     const uint4 zero4 = make_uint4(0, 0, 0, 0);
     if (!direct) {
-        for (uint32_t w = threadIdx.x; w < (1u << (pshift - 3)); w += kApplyThreads) smem[w] = 0;
+        for (uint32_t w = threadIdx.x; w < (1u << (g.shift - 3)); w += kApplyThreads) smem[w] = 0;
         if (threadIdx.x == 0) *carried = 0;
         __syncthreads();
         uint32_t over = 0;
-        const uint32_t hpart = h;
         auto half = [&](uint32_t lo, uint32_t hi) {  // 3 x 20-bit slice-local indices, valid count in bits 60..63
             const unsigned long long h = ((unsigned long long)hi << 32) | lo;
             const uint32_t nv = hi >> 28;
-            const uint32_t xx[3] = {(uint32_t)h & 0xFFFFFu, (uint32_t)(h >> 20) & 0xFFFFFu, (uint32_t)(h >> 40) & 0xFFFFFu};
-            uint32_t old[3] = {0, 0, 0}, x[3];
+            const uint32_t x[3] = {(uint32_t)h & 0xFFFFFu, (uint32_t)(h >> 20) & 0xFFFFFu, (uint32_t)(h >> 40) & 0xFFFFFu};
+            uint32_t old[3] = {0, 0, 0};
             bool mine[3];
 #pragma unroll
-            for (int e = 0; e < 3; ++e) {
-                mine[e] = (uint32_t)e < nv && (xx[e] >> pshift) == hpart;
-                x[e] = xx[e] & pmask;
-            }
+            for (int e = 0; e < 3; ++e) mine[e] = (uint32_t)e < nv && (x[e] >> g.shift) == 0;  // (an index past the slice: not applied)
 #pragma unroll
             for (int e = 0; e < 3; ++e)
-                if (mine[e]) old[e] = atomicAdd(&smem[dlt_word<BLOCKS>(x[e])], 1u << dlt_bit<BLOCKS>(x[e]));  // ds_add_rtn_u32
+                if (mine[e]) old[e] = atomicAdd(&smem[dlt_word(x[e])], 1u << dlt_bit(x[e]));  // ds_add_rtn_u32
 #pragma unroll
             for (int e = 0; e < 3; ++e)
-                if (mine[e]) over |= (uint32_t)(((old[e] >> dlt_bit<BLOCKS>(x[e])) & 15u) == 15u);
+                if (mine[e]) over |= (uint32_t)(((old[e] >> dlt_bit(x[e])) & 15u) == 15u);
         };
         for_each_group<kNibDepth>(buckets, segcnt, g, b, zero4, [&](const uint4 q) { half(q.x, q.y); half(q.z, q.w); });
         if (over) *carried = 1u;
         __syncthreads();
     }
     if (direct || *carried) {  // uniform: exact atomics for this slice, straight from its probe groups
-        const uint32_t hpart2 = h;
         auto slow = [&](uint32_t lo, uint32_t hi) {
             const unsigned long long h = ((unsigned long long)hi << 32) | lo;
             const uint32_t nv = hi >> 28;
 #pragma unroll
             for (int e = 0; e < 3; ++e) {
                 const uint32_t xe = (uint32_t)(h >> (20 * e)) & 0xFFFFFu;
-                if ((uint32_t)e < nv && (xe >> pshift) == hpart2) {
-                    const uint64_t cell = c0 + (xe & pmask);
-                    if (OPT == 1) {
-                        const uint32_t old = atomicSub(tab + cell, 1u);
-                        bad |= (uint32_t)(old == 0u) | (uint32_t)(old == 0xFFFFFFFFu);
-                    } else if (OPT == 2) {
-                        atomicAdd(tab + cell, 1u);
-                    } else if (NEG) cbf_sat_sub(tab + cell, 1u, sat_ctr - 1);
+                if ((uint32_t)e < nv && (xe >> g.shift) == 0) {
+                    const uint64_t cell = c0 + xe;
+                    if (NEG) cbf_sat_sub(tab + cell, 1u, sat_ctr - 1);
                     else cbf_sat_add(tab + cell, 1u, sat_ctr);
                 }
             }
         };
         for_each_group<kNibDepth>(buckets, segcnt, g, b, zero4, [&](const uint4 q) { slow(q.x, q.y); slow(q.z, q.w); });
-        if (OPT == 1 && bad) *flag = 1u;
         return;
     }
     unsigned long long sat = 0, viol = 0;
     auto fold = [&](uint32_t t, uint32_t d) -> uint32_t {
         if (d == 0) return t;
-        if (OPT == 1) {
-            bad |= (uint32_t)(t < d) | (uint32_t)(t == 0xFFFFFFFFu);
-            return t - d;
-        }
-        if (OPT == 2) return t + d;
         if (NEG) {  // countingbloom.py:203-206: a counter frozen at 2^32-1 stays; below zero = the stream was not well-formed
             if (t == 0xFFFFFFFFu) return t;
             if (t < d) { ++viol; return 0u; }
@@ -366,76 +337,51 @@ __device__ __forceinline__ void nib_apply_list(uint32_t *smem, uint32_t *carried
         if (gc + 1 < tab_cells) tab[gc + 1] = o.y;
         if (gc + 2 < tab_cells) tab[gc + 2] = o.z;
     };
-    if constexpr (BLOCKS) {
-        const uint32_t blocks = 1u << (pshift - 13);
-        constexpr int U = 2;  // blocks (two 16-byte pieces per lane each) in flight (two workgroups per CU: 64 VGPRs per lane)
-        for (uint32_t k0 = 0; k0 < blocks; k0 += U) {
-            uint32_t d[U];
-            uint4 t[U][2];
+    // (plain table loads: the fold re-writes what it reads, and measured slower with nontemporal ones, 795 -> 984 us)
+    const uint32_t blocks = 1u << (g.shift - 13);
+    constexpr int U = 2;  // blocks (two 16-byte pieces per lane each) in flight (two workgroups per CU: 64 VGPRs per lane)
+    for (uint32_t k0 = 0; k0 < blocks; k0 += U) {
+        uint32_t d[U];
+        uint4 t[U][2];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {  // (slices of 2^15 counters and more: blocks is a multiple of U = 4)
-                const uint64_t gc = c0 + (uint64_t)(k0 + u) * 8192u + 4u * threadIdx.x;
-                d[u] = smem[(k0 + u) * 1024u + threadIdx.x];
-                t[u][0] = t[u][1] = zero4;
-                if (d[u] & 0xFFFFu) t[u][0] = nib_load_piece(tab, tab_cells, gc, nt);
-                if (d[u] >> 16) t[u][1] = nib_load_piece(tab, tab_cells, gc + 4096u, nt);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint64_t gc = c0 + (uint64_t)(k0 + u) * 8192u + 4u * threadIdx.x;
-                if (d[u] & 0xFFFFu) store_piece(gc, fold4(t[u][0], d[u] & 0xFFFFu));
-                if (d[u] >> 16) store_piece(gc + 4096u, fold4(t[u][1], d[u] >> 16));
-            }
+        for (int u = 0; u < U; ++u) {  // (slices of 2^15 counters and more: blocks is a multiple of U = 4)
+            const uint64_t gc = c0 + (uint64_t)(k0 + u) * 8192u + 4u * threadIdx.x;
+            d[u] = smem[(k0 + u) * 1024u + threadIdx.x];
+            t[u][0] = t[u][1] = zero4;
+            if (d[u] & 0xFFFFu) t[u][0] = nib_load_piece(tab, tab_cells, gc);
+            if (d[u] >> 16) t[u][1] = nib_load_piece(tab, tab_cells, gc + 4096u);
         }
-    } else {
-        const uint16_t *half16 = reinterpret_cast<const uint16_t *>(smem);
-        constexpr int U = 2;  // 16-byte pieces in flight per lane
-        for (uint32_t p0 = threadIdx.x; p0 < pieces; p0 += kApplyThreads * U) {
-            uint32_t d[U];
-            uint4 t[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint32_t pc = p0 + (uint32_t)u * kApplyThreads;
-                d[u] = pc < pieces ? (uint32_t)half16[pc] : 0u;
-                t[u] = zero4;
-                if (d[u]) t[u] = nib_load_piece(tab, tab_cells, c0 + 4ULL * pc, nt);  // untouched pieces are neither read nor written
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint32_t pc = p0 + (uint32_t)u * kApplyThreads;
-                if (d[u]) store_piece(c0 + 4ULL * pc, fold4(t[u], d[u]));
-            }
+        for (int u = 0; u < U; ++u) {
+            const uint64_t gc = c0 + (uint64_t)(k0 + u) * 8192u + 4u * threadIdx.x;
+            if (d[u] & 0xFFFFu) store_piece(gc, fold4(t[u][0], d[u] & 0xFFFFu));
+            if (d[u] >> 16) store_piece(gc + 4096u, fold4(t[u][1], d[u] >> 16));
         }
     }
     if (sat) atomicAdd(sat_ctr, sat);
     if (viol) atomicAdd(sat_ctr - 1, viol);
-    if (OPT == 1 && bad) *flag = 1u;
 }
 
 // MODE 0: the list is adds; 1: decrements; 2: list A adds, THEN list B decrements (one launch for a write-combined flush: the
-// slice a workgroup has just folded is still on-die when it folds it again); 3: optimistic decrement (flag), 4: its inverse.
-// direct: see nib_apply_list.
-template <int MODE, bool BLOCKS>
+// slice a workgroup has just folded is still on-die when it folds it again).
+// direct != 0: atomics instead of the image, see nib_apply_list.
+template <int MODE>
 __global__ __launch_bounds__(kApplyThreads, 8) void k_nib_apply(uint32_t *tab, uint64_t tab_cells, PartGeom g, const uint32_t *segcnt_a, const uint4 *buckets_a,
                                                              const uint32_t *segcnt_b, const uint4 *buckets_b, unsigned long long *sat_ctr, uint32_t direct,
-                                                             uint32_t *flag, PartGeom gb)
+                                                             PartGeom gb)
 {
     // gb: geometry of list B (MODE 2; same slices as g, its own workgroup count / segment capacity)
-    // direct: bit 0 = atomics instead of the image, bit 1 = nontemporal table loads, bits 8.. = log2(workgroups per slice), see nib_apply_list
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     __shared__ uint32_t carried;
-    const uint32_t lgp = direct >> 8;
-    const uint32_t b = blockIdx.x >> lgp, h = blockIdx.x & ((1u << lgp) - 1u);
-    if (((uint64_t)b << g.shift) + ((uint64_t)h << (g.shift - lgp)) >= tab_cells) return;  // (a part past the table's end)
-    if (MODE == 0 || MODE == 2) nib_apply_list<false, BLOCKS>(smem, &carried, tab, tab_cells, g, segcnt_a, buckets_a, sat_ctr, b, (direct & 1u) != 0, (direct & 2u) != 0, nullptr, lgp, h);
+    const uint32_t b = blockIdx.x;
+    if (((uint64_t)b << g.shift) >= tab_cells) return;  // (a slice past the table's end)
+    if (MODE == 0 || MODE == 2) nib_apply_list<false>(smem, &carried, tab, tab_cells, g, segcnt_a, buckets_a, sat_ctr, b, direct != 0);
     if (MODE == 2) {
         __threadfence();   // my stores to the slice are visible to my loads below (same CU, but through L2: not the L1)
         __syncthreads();
     }
-    if (MODE == 1) nib_apply_list<true, BLOCKS>(smem, &carried, tab, tab_cells, g, segcnt_a, buckets_a, sat_ctr, b, (direct & 1u) != 0, (direct & 2u) != 0, nullptr, lgp, h);
-    if (MODE == 2) nib_apply_list<true, BLOCKS>(smem, &carried, tab, tab_cells, gb, segcnt_b, buckets_b, sat_ctr, b, (direct & 1u) != 0, (direct & 2u) != 0, nullptr, lgp, h);
-    if (MODE == 3) nib_apply_list<true, BLOCKS, 1>(smem, &carried, tab, tab_cells, g, segcnt_a, buckets_a, sat_ctr, b, (direct & 1u) != 0, (direct & 2u) != 0, flag, lgp, h);
-    if (MODE == 4) nib_apply_list<false, BLOCKS, 2>(smem, &carried, tab, tab_cells, g, segcnt_a, buckets_a, sat_ctr, b, (direct & 1u) != 0, (direct & 2u) != 0, flag, lgp, h);
+    if (MODE == 1) nib_apply_list<true>(smem, &carried, tab, tab_cells, g, segcnt_a, buckets_a, sat_ctr, b, direct != 0);
+    if (MODE == 2) nib_apply_list<true>(smem, &carried, tab, tab_cells, gb, segcnt_b, buckets_b, sat_ctr, b, direct != 0);
 }
 
 

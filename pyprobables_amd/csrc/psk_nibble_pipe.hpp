@@ -1,5 +1,5 @@
 // psk_nibble_pipe.hpp -- the pass over a big CountingBloomFilter table as a software pipeline (round 4): k_nib_apply's successor for the
-// default delta-image layout.  Included by the update launchers only (psk_part_counter.hpp).
+// table passes of the unit adds and the validated remove.  Included by the update launchers only (psk_part_counter.hpp).
 #pragma once
 #include "psk_nibble.hpp"
 
@@ -103,12 +103,13 @@ struct SegWalk {
 
 constexpr int kPipeDepth = 4;     // probe groups in flight per lane
 constexpr int kPipeWords = 32;    // image words per lane at most: slices of 2^18 counters
-// MODE 0: adds; 1: decrements; 3: optimistic decrement (flag); 4: its inverse -- as k_nib_apply's.  BLOCKS layout of the delta image
-// (dlt_word<true> / dlt_bit<true>): word (block k, lane t) = the pieces t and 1024 + t of block k (8192 counters).
+// MODE 0: adds; 1: decrements; 3: optimistic decrement (flag, psk_nibble.hpp); 4: its inverse.  The delta image of k_nib_apply
+// (dlt_word / dlt_bit): word (block k, lane t) = the pieces t and 1024 + t of block k (8192 counters).  Nontemporal table accesses
+// (551 -> 514 us per 10 M adds).
 // Grid: min(slices, CUs) persistent workgroups; slice b, b + gridDim.x, ...
 template <int MODE>
 __global__ __launch_bounds__(kApplyThreads, 4) void k_nib_apply_pipe(uint32_t *tab, uint64_t tab_cells, PartGeom g, const uint32_t *segcnt, const uint4 *buckets,
-                                                                    unsigned long long *sat_ctr, uint32_t nt, uint32_t *flag)
+                                                                    unsigned long long *sat_ctr, uint32_t *flag)
 {
     constexpr bool NEG = MODE == 1 || MODE == 3;
     constexpr int OPT = MODE == 3 ? 1 : (MODE == 4 ? 2 : 0);
@@ -129,10 +130,10 @@ __global__ __launch_bounds__(kApplyThreads, 4) void k_nib_apply_pipe(uint32_t *t
         uint32_t old[3] = {0, 0, 0};
 #pragma unroll
         for (int e = 0; e < 3; ++e)
-            if ((uint32_t)e < nv) old[e] = atomicAdd(&smem[dlt_word<true>(x[e])], 1u << dlt_bit<true>(x[e]));  // ds_add_rtn_u32
+            if ((uint32_t)e < nv) old[e] = atomicAdd(&smem[dlt_word(x[e])], 1u << dlt_bit(x[e]));  // ds_add_rtn_u32
 #pragma unroll
         for (int e = 0; e < 3; ++e)
-            if ((uint32_t)e < nv) over |= (uint32_t)(((old[e] >> dlt_bit<true>(x[e])) & 15u) == 15u);
+            if ((uint32_t)e < nv) over |= (uint32_t)(((old[e] >> dlt_bit(x[e])) & 15u) == 15u);
     };
     auto apply = [&](const uint4 (&q)[D]) {
 #pragma unroll
@@ -191,13 +192,9 @@ __global__ __launch_bounds__(kApplyThreads, 4) void k_nib_apply_pipe(uint32_t *t
     };
     auto store_piece = [&](uint64_t gc, const uint4 &o) {
         if (gc + 3 < tab_cells) {
-            if (nt) {
-                psk_u32x4 v;
-                v.x = o.x; v.y = o.y; v.z = o.z; v.w = o.w;
-                __builtin_nontemporal_store(v, reinterpret_cast<psk_u32x4 *>(tab + gc));
-            } else {
-                *reinterpret_cast<uint4 *>(tab + gc) = o;
-            }
+            psk_u32x4 v;
+            v.x = o.x; v.y = o.y; v.z = o.z; v.w = o.w;
+            __builtin_nontemporal_store(v, reinterpret_cast<psk_u32x4 *>(tab + gc));
             return;
         }
         if (gc + 0 < tab_cells) tab[gc + 0] = o.x;  // the table ends inside this piece
@@ -266,8 +263,8 @@ __global__ __launch_bounds__(kApplyThreads, 4) void k_nib_apply_pipe(uint32_t *t
                 // per-lane test -- 65 % of the pieces of a 10 M-key batch, scattered 16-byte writes into lines read in part -- reached 3.8.
                 touch[u][0] = __any((dl[u] & 0xFFFFu) != 0u);
                 touch[u][1] = __any((dl[u] >> 16) != 0u);
-                if (touch[u][0]) t[u][0] = nib_load_piece(tab, tab_cells, gc, nt != 0);
-                if (touch[u][1]) t[u][1] = nib_load_piece(tab, tab_cells, gc + 4096u, nt != 0);
+                if (touch[u][0]) t[u][0] = nib_load_piece(tab, tab_cells, gc, true);
+                if (touch[u][1]) t[u][1] = nib_load_piece(tab, tab_cells, gc + 4096u, true);
             }
             // a probe step of the next slice under every other fold step (a slice brings 2-3 steps per wave at 10 M keys)
             uint4 q[D];
@@ -296,139 +293,6 @@ __global__ __launch_bounds__(kApplyThreads, 4) void k_nib_apply_pipe(uint32_t *t
     if (sat) atomicAdd(sat_ctr, sat);
     if (viol) atomicAdd(sat_ctr - 1, viol);
     if (OPT == 1 && bad) *flag = 1u;
-}
-
-// ------------------------------------------------------------------------------------ lookups: the slice load under the probe walk
-// k_nib_gather's two phases -- load 1 MiB of table and pack it to nibbles; answer the slice's probe groups from the image -- follow each
-// other in a workgroup that holds the whole CU (128 KiB image): 292 us per 10 M keys where the table read alone takes 155-173 us
-// (scripts/ubench/tabpass.hip).  Here the NEXT slice of a persistent workgroup is loaded and packed into registers (64 pieces per lane ->
-// 64 halves = 32 VGPRs) while the current slice's probe groups are answered; two barriers hand the registers over to the image.
-// Image layout and kept images (shadow_out) exactly as k_nib_gather; the host takes this kernel when no kept images exist to load.
-template <int DUMMY = 0>
-__global__ __launch_bounds__(kApplyThreads, 4) void k_nib_gather_pipe(const uint32_t *tab, uint64_t tab_cells, PartGeom g, const uint32_t *segcnt, const uint4 *buckets,
-                                                                     uint32_t *vals, uint32_t nt, uint32_t *shadow_out)
-{
-    constexpr int D = 3;   // probe groups in flight per lane
-    constexpr int LP = 4;  // table pieces in flight per lane (one load step).  Registers bound both: 32 words of the next image + LP x 4 + D x (4 + 6 LDS words);
-                           // LP = 8 with D = 2 spilled and ran at 366 us, two steps of four in flight (double-buffered) spilled as well
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    uint16_t *half16 = reinterpret_cast<uint16_t *>(smem);
-    const uint32_t pieces = 1u << (g.shift - 2);           // 16-byte pieces of a slice = 16-bit halves of its image
-    const uint32_t nsteps = pieces / (kApplyThreads * LP);  // load steps per slice (1 .. 8)
-    const uint32_t vecs = 1u << (g.shift - 5);              // 16-byte units of an image
-    const uint4 zero4 = make_uint4(0, 0, 0, 0);
-    uint32_t r[kPipeWords];  // the next image, two halves per word: word k = pieces t + 1024 * 2k (low) and t + 1024 * (2k + 1) (high) of lane t
-#pragma unroll
-    for (int k = 0; k < kPipeWords; ++k) r[k] = 0;
-
-    auto slice_ok = [&](uint32_t b) { return b < g.nbuckets && ((uint64_t)b << g.shift) < tab_cells; };
-    // one load step of slice b: pieces t + 1024 * (LP j + 0 .. LP - 1)
-    // `whole`: the slice lies inside the table (all but possibly the last): a uniform base + the lane's offset, no per-piece bound test
-    auto whole = [&](uint32_t b) { return (((uint64_t)b + 1) << g.shift) <= tab_cells; };
-    auto issue = [&](uint4 (&t)[LP], uint32_t b, uint32_t j) {
-        const psk_u32x4 *sb = reinterpret_cast<const psk_u32x4 *>(tab + ((uint64_t)b << g.shift)) + (size_t)kApplyThreads * LP * j;  // uniform
-#pragma unroll
-        for (int u = 0; u < LP; ++u) {
-            const psk_u32x4 v = nt ? __builtin_nontemporal_load(sb + kApplyThreads * u + threadIdx.x) : sb[kApplyThreads * u + threadIdx.x];
-            t[u] = make_uint4(v.x, v.y, v.z, v.w);
-        }
-    };
-    auto issue_tail = [&](uint4 (&t)[LP], uint32_t b, uint32_t j) {  // the slice the table ends in
-        const uint64_t c0 = (uint64_t)b << g.shift;
-#pragma unroll
-        for (int u = 0; u < LP; ++u) t[u] = nib_load_piece(tab, tab_cells, c0 + 4ULL * (threadIdx.x + kApplyThreads * ((uint32_t)LP * j + (uint32_t)u)), nt != 0);
-    };
-    auto pack = [&](const uint4 (&t)[LP]) {  // the words rotate down by LP / 2; the step's words come in at the top
-#pragma unroll
-        for (int k = 0; k + LP / 2 < kPipeWords; ++k) r[k] = r[k + LP / 2];
-#pragma unroll
-        for (int u = 0; u < LP / 2; ++u) r[kPipeWords - LP / 2 + u] = nib_pack4(t[2 * u]) | (nib_pack4(t[2 * u + 1]) << 16);
-    };
-    auto load_plain = [&](uint32_t b) {  // a slice into the registers, nothing overlapped
-        for (uint32_t j = 0; j < nsteps; ++j) {
-            uint4 t[LP];
-            if (whole(b)) issue(t, b, j);
-            else issue_tail(t, b, j);
-            pack(t);
-        }
-    };
-    // registers -> image: after `nsteps` steps the slice's words sit in r[32 - (LP / 2) nsteps .. 32)
-    auto hand_over = [&]() {
-#pragma unroll
-        for (int k = 0; k < kPipeWords; ++k) {
-            const int first = kPipeWords - (LP / 2) * (int)nsteps;  // (uniform)
-            if (k >= first) {
-                const uint32_t u2 = (uint32_t)(k - first);
-                half16[threadIdx.x + kApplyThreads * (2u * u2)] = (uint16_t)(r[k] & 0xFFFFu);
-                half16[threadIdx.x + kApplyThreads * (2u * u2 + 1u)] = (uint16_t)(r[k] >> 16);
-            }
-        }
-    };
-    auto answer = [&](const uint4 (&q)[D], const uint32_t (&at)[D]) {
-        uint32_t w[D][6];
-#pragma unroll
-        for (int d = 0; d < D; ++d)  // the LDS reads of the whole step first (slots past a run's end read counter 0: harmless)
-#pragma unroll
-            for (int e = 0; e < 6; ++e) w[d][e] = smem[nib_word(group_field(q[d], e))];
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            if (at[d] != 0xFFFFFFFFu) {
-                uint32_t rr = 0;
-#pragma unroll
-                for (int e = 0; e < 6; ++e) rr |= ((w[d][e] >> nib_bit(group_field(q[d], e))) & 15u) << (4 * e);
-                vals[at[d]] = rr;
-            }
-        }
-    };
-
-    // ---- my first slice: load, pack, hand over (nothing to overlap with yet)
-    if (!slice_ok(blockIdx.x)) return;
-    load_plain(blockIdx.x);
-    hand_over();
-    __syncthreads();
-    for (uint32_t b = blockIdx.x; slice_ok(b); b += gridDim.x) {
-        if (shadow_out) {  // (the stores drain under the probe walk below)
-            uint4 *dst = reinterpret_cast<uint4 *>(shadow_out) + (uint64_t)b * vecs;
-            const uint4 *src = reinterpret_cast<const uint4 *>(smem);
-            for (uint32_t pc = threadIdx.x; pc < vecs; pc += kApplyThreads) dst[pc] = src[pc];
-        }
-        const uint32_t nb = b + gridDim.x;
-        const bool next_any = slice_ok(nb);
-        const bool have_next = next_any && whole(nb);  // (the slice the table ends in is loaded behind the walk, unpipelined)
-        SegWalk<D> walk;
-        walk.init(buckets, segcnt, g, b);
-        // every load step of the next slice is followed by probe steps of this one: the pieces land while the groups are answered
-        const uint32_t per = 1;  // probe steps per load step (a slice brings ~4 steps of three groups per wave at 10 M keys)
-        if (have_next) {
-            for (uint32_t j = 0; j < nsteps; ++j) {
-                // (the probe groups are requested BEFORE the pieces: vmcnt counts in order, so waiting for the groups leaves the pieces in flight)
-                uint4 q[D];
-                uint32_t at[D];
-                const bool had = walk.more();  // (uniform)
-                if (had) walk.next_at(q, at, zero4);
-                uint4 t[LP];
-                issue(t, nb, j);
-                if (had) answer(q, at);
-                for (uint32_t e = 1; e < per && walk.more(); ++e) {
-                    uint4 q2[D];
-                    uint32_t at2[D];
-                    walk.next_at(q2, at2, zero4);
-                    answer(q2, at2);
-                }
-                pack(t);
-            }
-        }
-        while (walk.more()) {
-            uint4 q[D];
-            uint32_t at[D];
-            walk.next_at(q, at, zero4);
-            answer(q, at);
-        }
-        if (next_any && !have_next) load_plain(nb);
-        __syncthreads();  // every wave is done with this slice's image
-        if (next_any) hand_over();
-        __syncthreads();
-    }
 }
 
 }  // namespace psk

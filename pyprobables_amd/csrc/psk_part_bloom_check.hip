@@ -6,7 +6,7 @@
 // (the table is not consulted; an overflowing segment raises *defer instead of testing its probes directly)
 // Pass 1 workgroups of the keyed lookups.  A round holds 16 tiles per workgroup (PayKeyId) and pass 2 reads the whole table
 // once per round: with 2048 slices (m = 2^31: 256 MiB per round) four times the workgroups -- 33.5 M keys per round -- is worth
-// +13 % (256 workgroups 21.0, 512: 22.7, 1024: 23.8 G keys/s; scripts/ab_wgs.py, scripts/ab_2p31_lookup.py); at 1024 slices and
+// +13 % (256 workgroups 21.0, 512: 22.7, 1024: 23.8 G keys/s; NOTES.md §3.2); at 1024 slices and
 // below it measures the same or slightly worse.
 static inline uint32_t keyed_wgs(const PartGeom &g) { return g.nbuckets >= 2048 ? 1024u : 0u; }  // 0: launch_scatter's default
 
@@ -44,7 +44,7 @@ static bool check_geometry(psk_sketch *s, const Batch &b, PartGeom *g, uint64_t 
     uint64_t rk = part_round_keys_big_table(n, s->k, PayKeyId::group, s->padded_bytes);
     // a keyed group spells the tile's ordinal inside its workgroup in 4 bits: at most 16 tiles per workgroup and round
     // (256 workgroups x 16 x 2048-key tiles for k <= 8; 512-key tiles beyond)
-    uint64_t cap = (uint64_t)PayKeyId::max_tiles_per_wg * (g_part_wgs > 0 ? (uint64_t)(g_part_wgs < 1024 ? g_part_wgs : 1024) : (keyed_wgs(*g) ? keyed_wgs(*g) : 256u)) *
+    uint64_t cap = (uint64_t)PayKeyId::max_tiles_per_wg * (keyed_wgs(*g) ? keyed_wgs(*g) : 256u) *
                    (s->k <= 8 ? (g_part_tile_threads == 512 ? 1024 : 2048) : 512);  // (forced 512-thread tiles hold 1024 keys at k = 7, 8)
     // ... of the tile launch_scatter_nt will really run: it cuts the tile where the LDS stage -- plus the per-tile length sort of ragged keys --
     // would not fit (e.g. 1280 keys at 2048 slices), and a round sized for 2048-key tiles would then need more than 16 tiles per workgroup
@@ -151,7 +151,7 @@ static bool tile_flag_geometry(psk_sketch *s, const Batch &b, PartGeom *g, uint6
                 // pass 2, up to 1024 (m = 2^31: a 2^25-key lookup was four rounds, four 256 MiB sweeps of 127 us)
                 uint32_t want = src_fat512<Src>::value ? 0u : 512u;
                 cap = scatter_round_cap<PayTileTag, KT, src_fat512<Src>::value, src_sorted<Src>::value>(g, want, PayTileTag::max_tiles_per_wg);
-                if (s->padded_bytes >= (64ULL << 20) && g_part_wgs <= 0) {
+                if (s->padded_bytes >= (64ULL << 20)) {
                     while (round_keys > cap && want < 1024u) {
                         want = want ? want * 2 : 512u;
                         const uint64_t c2 = scatter_round_cap<PayTileTag, KT, src_fat512<Src>::value, src_sorted<Src>::value>(g, want, PayTileTag::max_tiles_per_wg);

@@ -20,12 +20,6 @@ int PSK_VARIANT(cbf_scat_append)(psk_sketch *s, const Batch &b, int neg, hipStre
     return PSK_OK;
 }
 
-// pass 1 alone (fused flush of the write-combined lists: psk_capi.hip flush_combined)
-int PSK_VARIANT(cbf_nib_scatter)(psk_sketch *s, const Batch &b, int neg, int second, PartGeom *g_out, hipStream_t st, bool *done)
-{
-    return cbf_nib_scatter_only(s, b, neg != 0, second != 0, g_out, st, done);
-}
-
 // The unchecked decrement of every index by the key's weight: what countingbloom.py:186-208 does for a well-formed stream
 // (min_val >= num_els, so to_remove == num_els); frozen counters stay, a counter that would go below zero is tallied as a
 // contract violation (k_counter_apply's fold).  Used by the write-combined update path.

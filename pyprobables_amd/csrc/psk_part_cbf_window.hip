@@ -2,11 +2,8 @@
 #include "psk_part_counter.hpp"
 #include "psk_window.hpp"
 
-extern PSK_HIDDEN int64_t g_window_nt;     // psk_capi.hip: option "update_window_nt"
-extern PSK_HIDDEN int64_t g_window_image;  // psk_capi.hip: option "update_window_image"
 extern PSK_HIDDEN int64_t g_window_wide;   // option "update_window_wide"
 extern PSK_HIDDEN int64_t g_window_tile;   // option "update_window_tile": 0 = by the rule in window_scatter, 2048 / 4096 = forced (A/B)
-extern PSK_HIDDEN int64_t g_window_shadow, g_window_shadow_writes;  // options "update_window_shadow" / "update_window_shadow_writes" (read-only tally)
 
 // Tables of the window's pass 1 and fold (pinned staging + device copy, one contiguous upload): [0 .. kWinMaxPhases] the fold's phases,
 // behind them the pieces of pass 1 (PhaseDesc in psk_partition.hpp).
@@ -112,8 +109,8 @@ int PSK_VARIANT(cbf_window_fold)(psk_sketch *s, const WinBatchHost *wb, uint32_t
     if (g_update_nibble == 0 || nb == 0 || s->k > 32 || !nib_geometry(s->m, true, &g)) return PSK_OK;
     g.k = s->k;
     PSK_TRY(ensure(s->s_flag, 8));
-    uint32_t *flag = (uint32_t *)s->s_flag.p;  // [0] a remove met a zero (undo + replay), [1] a slice took the atomics (its 4-bit image is void)
-    HIP_TRY(hipMemsetAsync(flag, 0, 8, st));
+    uint32_t *flag = (uint32_t *)s->s_flag.p;  // a remove met a zero (undo + replay)
+    HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
     uint32_t nph_dev = 0;  // phases of the fold (0: the window does not fit -- nothing was launched)
     PSK_TRY(with_kt<KeysFixed16>(s->k, [&](auto kt) {
         constexpr int KT = decltype(kt)::value;
@@ -126,50 +123,34 @@ int PSK_VARIANT(cbf_window_fold)(psk_sketch *s, const WinBatchHost *wb, uint32_t
     if (nph_dev == 0) return PSK_OK;
     *launched = true;
     const WinPhases wp{nph_dev, (const PhaseDesc *)s->s_phase.p};
-    const bool nib = g_window_image != 8;  // option "update_window_image": 4 (default) = nibble images, one workgroup per slice; 8 = byte images, two
-    const uint32_t pshift = win_part_shift(g.shift, nib);
-    const uint32_t parts = g.nbuckets << (g.shift - pshift);
     // tables of few slices (a 2048-key tile brings more than 4 probe groups per slice: below ~600 slices): the WIDE fold -- five groups per lane
     // and phase, byte-wide group counts -- when its count table still fits the LDS next to the image
     const double groups_per_tile = 2048.0 * (double)(s->k < 8 ? s->k : 8) / (double)g.nbuckets / 6.0 + 0.5;
     // (per segment and phase the narrow fold holds 12 groups: one tile of more than 4 groups per slice, or two tiles of more than 3.25 -- 732 slices:
     // 2 x 3.8, most slices overflowed, 9.4 -> 15.9 G ops/s with the wide fold; 1024 slices, BASELINE cfg 4: 2 x 2.8 fit, and the wide fold costs 5 %)
-    const bool wide = nib && g_window_wide != 0 && (groups_per_tile > 3.25 || g_window_wide == 2) && win_fold_lds(g, nph_dev, nib, true) <= 160 * 1024;  // (2: wherever it fits, A/B)
-    const size_t lds = win_fold_lds(g, nph_dev, nib, wide);
+    const bool wide = g_window_wide != 0 && (groups_per_tile > 3.25 || g_window_wide == 2) && win_fold_lds(g, nph_dev, true) <= 160 * 1024;  // (2: wherever it fits, A/B)
+    const size_t lds = win_fold_lds(g, nph_dev, wide);
     if (lds > 160 * 1024) return fail(PSK_EINVAL, "update window: %u phases of %u segments do not fit the fold's LDS", nph_dev, g.nwg);
-    PSK_TRY(ensure(s->s_wstat, (uint64_t)parts * 4));
-    // Kept 4-bit images (psk_sketch::shadow): when the lookups already keep them, the fold -- which ends with the very image of every slice
-    // in LDS -- leaves them up to date instead of stale: the lookup behind a flush loads 128 MiB instead of reading the 1 GiB table again.
-    const uint64_t shadow_words = (uint64_t)g.nbuckets << (g.shift - 3);
-    uint32_t *shadow_out = nullptr;
-    if (nib && pshift == g.shift && g_cbf_shadow != 0 && g_window_shadow != 0 && !s->shadow.exposed && s->shadow.img.p && s->shadow.words == shadow_words &&
-        s->shadow.img.cap >= shadow_words * 4)
-        shadow_out = (uint32_t *)s->shadow.img.p;
-    if (shadow_out) s->shadow.built = ~0ULL;  // (being overwritten: valid again only once the verdict is in)
+    PSK_TRY(ensure(s->s_wstat, (uint64_t)g.nbuckets * 4));
     {
-        auto kern = wide ? k_win_fold<false, true, 5> : (nib ? k_win_fold<false, true> : k_win_fold<false, false>);
+        auto kern = wide ? k_win_fold<false, 5> : k_win_fold<false>;
         PSK_TRY(set_dyn_lds(kern, lds));
-        hipLaunchKernelGGL(kern, dim3(parts), dim3(kApplyThreads), lds, st, (uint32_t *)s->table, s->m, g, (const uint4 *)s->s_part.p, (const uint32_t *)s->s_snap.p,
-                           wp, (uint32_t *)s->s_wstat.p, flag, (uint32_t)(g_window_nt != 0), shadow_out);
+        hipLaunchKernelGGL(kern, dim3(g.nbuckets), dim3(kApplyThreads), lds, st, (uint32_t *)s->table, s->m, g, (const uint4 *)s->s_part.p, (const uint32_t *)s->s_snap.p,
+                           wp, (uint32_t *)s->s_wstat.p, flag);
         HIP_TRY(hipGetLastError());
     }
     if (g_window_force_fail) HIP_TRY(hipMemsetAsync(flag, 1, 4, st));  // (tests: the undo + replay path on a well-formed stream)
-    uint32_t verdict[2] = {1, 1};
-    HIP_TRY(hipMemcpyAsync(verdict, flag, 8, hipMemcpyDeviceToHost, st));
+    uint32_t verdict = 1;
+    HIP_TRY(hipMemcpyAsync(&verdict, flag, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (verdict[0] == 0) {
+    if (verdict == 0) {
         *ok = true;
-        if (shadow_out) {  // every slice wrote its image (from LDS, or from the table behind its atomics): the kept images mirror the table as it is now
-            s->shadow.built = s->table_version;
-            s->shadow.stream = st;
-            ++g_window_shadow_writes;
-        }
         return PSK_OK;
     }
-    auto kern = nib ? k_win_fold<true, true> : k_win_fold<true, false>;  // the proof failed: put every part back where it was
+    auto kern = k_win_fold<true>;  // the proof failed: put every slice back where it was
     PSK_TRY(set_dyn_lds(kern, lds));
-    hipLaunchKernelGGL(kern, dim3(parts), dim3(kApplyThreads), lds, st, (uint32_t *)s->table, s->m, g, (const uint4 *)s->s_part.p, (const uint32_t *)s->s_snap.p, wp,
-                       (uint32_t *)s->s_wstat.p, flag, (uint32_t)(g_window_nt != 0), (uint32_t *)nullptr);
+    hipLaunchKernelGGL(kern, dim3(g.nbuckets), dim3(kApplyThreads), lds, st, (uint32_t *)s->table, s->m, g, (const uint4 *)s->s_part.p, (const uint32_t *)s->s_snap.p, wp,
+                       (uint32_t *)s->s_wstat.p, flag);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
 }

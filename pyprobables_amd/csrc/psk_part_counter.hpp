@@ -87,35 +87,24 @@ static inline int nib_scatter(psk_sketch *s, const Batch &sub, const uint32_t *m
     });
 }
 
-extern PSK_HIDDEN int64_t g_nib_update_pipe;  // psk_capi.hip: option "nibble_update_pipe"
-// MODE: k_nib_apply's (0 adds, 1 decrements, 3 optimistic decrement with `flag`, 4 its inverse)
+// The pass over the table (psk_nibble_pipe.hpp: persistent workgroups, the fold of one slice under the probe groups of the next).
+// MODE: k_nib_apply_pipe's (0 adds, 1 decrements, 3 optimistic decrement with `flag`, 4 its inverse).  g comes from nib_geometry:
+// slices of 2^15 .. 2^18 counters, the shapes the kernel is written for.
 template <int MODE>
 static inline int nib_apply_mode(psk_sketch *s, const PartGeom &g, const void *cnt, const void *part, hipStream_t st, uint32_t *flag = nullptr)
 {
-    const uint32_t lgp = nib_update_lgparts(g);
-    // round 4: the pipelined pass (psk_nibble_pipe.hpp) -- persistent workgroups, the fold of one slice under the probe groups of the next;
-    // the blocks layout of the delta image, one workgroup per slice; option "nibble_update_pipe" (0 = k_nib_apply, the A/B partner)
-    if (g_nib_update_pipe != 0 && g_nib_update_layout != 0 && lgp == 0 && g.shift >= 15) {
-        static int ncu = 0;
-        if (ncu == 0) {
-            int dev = 0, v = 0;
-            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-            ncu = v;
-        }
-        const size_t lds_p = (size_t)1 << (g.shift - 1);
-        auto kp = k_nib_apply_pipe<MODE>;
-        PSK_TRY(set_dyn_lds(kp, lds_p));
-        const uint32_t grid = g.nbuckets < (uint32_t)ncu ? g.nbuckets : (uint32_t)ncu;
-        hipLaunchKernelGGL(kp, dim3(grid), dim3(kApplyThreads), lds_p, st, (uint32_t *)s->table, s->m, g, (const uint32_t *)cnt, (const uint4 *)part,
-                           (unsigned long long *)(s->ctr + PSK_CTR_SATURATED), (uint32_t)(g_nib_update_pipe != 3), flag);  // (3: plain instead of nontemporal table accesses, bench A/B)
-        HIP_TRY(hipGetLastError());
-        return PSK_OK;
+    static int ncu = 0;
+    if (ncu == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+        ncu = v;
     }
-    const size_t lds = (size_t)1 << (g.shift - 1 - lgp);
-    auto kern = g_nib_update_layout ? k_nib_apply<MODE, true> : k_nib_apply<MODE, false>;
-    PSK_TRY(set_dyn_lds(kern, lds));
-    hipLaunchKernelGGL(kern, dim3(g.nbuckets << lgp), dim3(kApplyThreads), lds, st, (uint32_t *)s->table, s->m, g, (const uint32_t *)cnt, (const uint4 *)part,
-                       (const uint32_t *)nullptr, (const uint4 *)nullptr, (unsigned long long *)(s->ctr + PSK_CTR_SATURATED), lgp << 8, flag, g);
+    const size_t lds = (size_t)1 << (g.shift - 1);
+    auto kp = k_nib_apply_pipe<MODE>;
+    PSK_TRY(set_dyn_lds(kp, lds));
+    const uint32_t grid = g.nbuckets < (uint32_t)ncu ? g.nbuckets : (uint32_t)ncu;
+    hipLaunchKernelGGL(kp, dim3(grid), dim3(kApplyThreads), lds, st, (uint32_t *)s->table, s->m, g, (const uint32_t *)cnt, (const uint4 *)part,
+                       (unsigned long long *)(s->ctr + PSK_CTR_SATURATED), flag);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
 }
@@ -123,26 +112,6 @@ template <bool NEG>
 static inline int nib_apply(psk_sketch *s, const PartGeom &g, const void *cnt, const void *part, hipStream_t st)
 {
     return nib_apply_mode<NEG ? 1 : 0>(s, g, cnt, part, st);
-}
-
-// Pass 1 alone of a unit-weight batch (one round) into the handle's first (second = false) or second bucket buffer: the fused flush of
-// the write-combined lists scatters both lists, then folds them in ONE launch (k_nib_apply<2>).  *done = false: not eligible.
-static inline int cbf_nib_scatter_only(psk_sketch *s, const Batch &b, bool neg, bool second, PartGeom *g_out, hipStream_t st, bool *done)
-{
-    *done = false;
-    const uint64_t cells = s->m;
-    if (g_update_nibble == 0 || !part_wanted(b.n, s->k, 4) || b.n > part_round_keys_two_level(b.n, s->k) || !nib_load_ok(b.n, s->k, cells)) return PSK_OK;
-    PartGeom g;
-    if (!nib_geometry(cells, true, &g)) return PSK_OK;
-    g.k = s->k;
-    if (second) { std::swap(s->s_part, s->s_part2); std::swap(s->s_cnt, s->s_cnt2); }  // (launch_scatter fills s_part / s_cnt)
-    bool handled = false;
-    const int rc = nib_scatter<false>(s, b, nullptr, neg, &g, st, &handled);
-    if (second) { std::swap(s->s_part, s->s_part2); std::swap(s->s_cnt, s->s_cnt2); }
-    PSK_TRY(rc);
-    *g_out = g;
-    *done = handled;
-    return PSK_OK;
 }
 
 // CountingBloomFilter unit-weight adds / decrements into 2^26 .. 2^29 counters: ONE level of 2^18-counter slices with 4-bit delta

@@ -4,9 +4,7 @@
 #include "psk_host.hpp"
 #include "psk_lookup.hpp"
 #include "psk_nibble.hpp"
-#include "psk_nibble_pipe.hpp"
 
-extern PSK_HIDDEN int64_t g_nib_gather_pipe;  // psk_capi.hip: option "nibble_lookup_pipe"
 extern PSK_HIDDEN int64_t g_cbf_shadow_hits;  // nibble-slice lookups that loaded kept images (psk_sketch::shadow)
 
 // Keys per round.  Measured on MI355X (10 M CMS lookups): one round of 10 M keys 432 us, two 446, three cache-sized ones 464
@@ -81,12 +79,10 @@ static inline int counter_check_partitioned(psk_sketch *s, const Batch &b, uint3
                 // of two that still fits ONE wave of workgroups (32 slices: 8 per slice; 160 slices, BASELINE cfg 3: none -- two per slice
                 // were 320 workgroups, a second wave of 64); between 256 and 1024 slices two per slice as before.
                 g2.split = 1;
-                if (g_lookup_split != 0) {
-                    if (g.nbuckets <= 256) {
-                        while (g2.split < 8 && g.nbuckets * g2.split * 2 <= 256) g2.split *= 2;
-                    } else if (g.nbuckets % 256 != 0 && g.nbuckets < 1024) {
-                        g2.split = 2;
-                    }
+                if (g.nbuckets <= 256) {
+                    while (g2.split < 8 && g.nbuckets * g2.split * 2 <= 256) g2.split *= 2;
+                } else if (g.nbuckets % 256 != 0 && g.nbuckets < 1024) {
+                    g2.split = 2;
                 }
                 hipLaunchKernelGGL(gather, dim3(g.nbuckets * g2.split), dim3(kApplyThreads), lds2, st, (const uint32_t *)s->table, cells, g2,
                                    (const uint32_t *)s->s_cnt.p, (const uint4 *)s->s_part.p, (uint4 *)s->s_vals.p, fmt, flag);
@@ -97,15 +93,14 @@ static inline int counter_check_partitioned(psk_sketch *s, const Batch &b, uint3
                 const size_t lds3 = ((size_t)2 * g.nbuckets + stage_cap) * 4 + ((g.nbuckets + 15) & ~(size_t)15);
                 const uint64_t ntiles = (cnt + g.tile - 1) / g.tile;
                 // pass 3 as 512-thread workgroups (four tiles in flight per CU) pays up to 256 slices (cfg 3: 270 -> 259 us per 10 M lookups) and
-                // costs 15 % at 1024 (twice the runinfo reads per key): option "lookup_collect_threads" 0 = this rule, 512 / 1024 = forced
-                const bool narrow_wg = g_lookup_collect_threads == 512 || (g_lookup_collect_threads == 0 && g.nbuckets <= 256);
+                // costs 15 % at 1024 (twice the runinfo reads per key)
+                const bool narrow_wg = g.nbuckets <= 256;
                 auto kern = narrow_wg ? k_lookup_collect<Query, KT, 512> : k_lookup_collect<Query, KT, 1024>;
                 PSK_TRY(set_dyn_lds(kern, lds3));
                 // lanes that copy one (tile, slice) run of values: the power of two at or above HALF the mean run -- a lane moves two
                 // 16-bit values at a time, the usual format; runs of 32-bit values take a second trip through the loop
                 uint32_t run_lanes = 4;
                 while (run_lanes < 64 && (uint64_t)run_lanes * 2 * g.nbuckets < (uint64_t)g.tile * kq) run_lanes *= 2;
-                if (g_lookup_run_lanes > 0) run_lanes = (uint32_t)g_lookup_run_lanes;
                 const uint64_t grid3 = narrow_wg ? 1024 : 512;
                 hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < grid3 ? ntiles : grid3)), dim3(narrow_wg ? 512 : 1024), lds3, st, query, g, cnt,
                                    (const uint32_t *)s->s_perm.p, (const uint2 *)s->s_run.p, (const uint32_t *)s->s_vals.p, (const uint8_t *)fmt, stage_cap, run_lanes,
@@ -186,26 +181,9 @@ static inline int cbf_check_nibble(psk_sketch *s, const Batch &b, uint32_t kk, u
                 const uint32_t kq = g.k < (uint32_t)KT ? g.k : (uint32_t)KT;
                 PSK_TRY(ensure(s->s_vals, (uint64_t)g.nbuckets * g.nwg * g.segcap * 4 + 256));  // one dword (six nibbles) per group
                 const size_t lds2 = (size_t)1 << (g.shift - 1);
-                if (g_nib_gather_pipe != 0 && shadow_in == nullptr && g.shift >= 15) {
-                    // round 4: no kept images to load -- the pipelined pass (psk_nibble_pipe.hpp: the next slice's table load under this
-                    // slice's probe walk); option "nibble_lookup_pipe" (0 = k_nib_gather, the A/B partner)
-                    static int ncu = 0;
-                    if (ncu == 0) {
-                        int dev = 0, v = 0;
-                        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-                        ncu = v;
-                    }
-                    auto kp = k_nib_gather_pipe<0>;
-                    PSK_TRY(set_dyn_lds(kp, lds2));
-                    const uint32_t grid = g.nbuckets < (uint32_t)ncu ? g.nbuckets : (uint32_t)ncu;
-                    hipLaunchKernelGGL(kp, dim3(grid), dim3(kApplyThreads), lds2, st, (const uint32_t *)s->table, cells, g, (const uint32_t *)s->s_cnt.p,
-                                       (const uint4 *)s->s_part.p, (uint32_t *)s->s_vals.p, (uint32_t)(g_nib_nt != 0), shadow_out);
-                } else {
-                    PSK_TRY(set_dyn_lds(k_nib_gather, lds2));
-                    hipLaunchKernelGGL(k_nib_gather, dim3(g.nbuckets), dim3(kApplyThreads), lds2, st, (const uint32_t *)s->table, cells, g,
-                                       (const uint32_t *)s->s_cnt.p, (const uint4 *)s->s_part.p, (uint32_t *)s->s_vals.p, (uint32_t)(g_nib_nt != 0), shadow_in,
-                                       shadow_out);
-                }
+                PSK_TRY(set_dyn_lds(k_nib_gather, lds2));
+                hipLaunchKernelGGL(k_nib_gather, dim3(g.nbuckets), dim3(kApplyThreads), lds2, st, (const uint32_t *)s->table, cells, g,
+                                   (const uint32_t *)s->s_cnt.p, (const uint4 *)s->s_part.p, (uint32_t *)s->s_vals.p, shadow_in, shadow_out);
                 HIP_TRY(hipGetLastError());
                 shadow_used = shadow_used || shadow_in != nullptr;
                 if (shadow_out) {  // the images are complete behind this launch: the next round / lookup on this stream loads them
@@ -223,7 +201,6 @@ static inline int cbf_check_nibble(psk_sketch *s, const Batch &b, uint32_t kk, u
                 PSK_TRY(set_dyn_lds(kern, lds3));
                 uint32_t run_lanes = 2;  // lanes (one dword = one group of 6 probes each) per (tile, slice) run
                 while (run_lanes < 64 && (uint64_t)run_lanes * 6 * g.nbuckets < (uint64_t)g.tile * kq + 6ULL * g.nbuckets) run_lanes *= 2;
-                if (g_lookup_run_lanes > 0) run_lanes = (uint32_t)g_lookup_run_lanes;
                 hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < 512 ? ntiles : 512)), dim3(kBloomCollectThreads), lds3, st, g, cnt, (const uint32_t *)s->s_perm.p,
                                    (const uint2 *)s->s_run.p, (const uint32_t *)s->s_vals.p, stage_groups, run_lanes, out_dev + start, amb);
                 HIP_TRY(hipGetLastError());

@@ -1407,7 +1407,6 @@ constexpr int kApplyDepth = 12;  // 16-byte loads in flight per lane
 // Tables far beyond the 256 MB Infinity Cache (BASELINE cfg 5: 256 MiB of bits per replica) are swept once per call: nontemporal accesses
 // keep the sweep from pushing the probe stream out of the cache (scripts/ubench/tabpass.hip: + 10 % on such a pass; round 4)
 constexpr uint64_t kNtTableWords = 1ULL << 25;  // 128 MiB
-constexpr uint32_t kGeomNtBit = 0x80000000u;    // PartGeom::dbg bit 31 (a production bit, not a bench knob): option "big_table_nt" is on
 __device__ __forceinline__ uint4 slice_piece(const uint32_t *tab, uint64_t tab_words, uint64_t w0, uint32_t w, bool nt = false)
 {
     const uint64_t gw = w0 + w;
@@ -1430,9 +1429,9 @@ __device__ __forceinline__ uint4 slice_piece(const uint32_t *tab, uint64_t tab_w
 // pieces a lane moves for a 128 KiB slice were 8 DEPENDENT round trips -- load, wait, LDS store -- in front of every pass-2
 // workgroup's work: round 3)
 constexpr int kSliceLoads = 8;
-__device__ __forceinline__ void load_slice(uint32_t *smem, const uint32_t *tab, uint64_t tab_words, uint64_t w0, uint32_t slice_words, bool nt_on = false)
+__device__ __forceinline__ void load_slice(uint32_t *smem, const uint32_t *tab, uint64_t tab_words, uint64_t w0, uint32_t slice_words)
 {
-    const bool nt = nt_on && tab_words >= kNtTableWords;
+    const bool nt = tab_words >= kNtTableWords;
     for (uint32_t wb = threadIdx.x * 4; wb < slice_words; wb += kApplyThreads * 4 * kSliceLoads) {
         uint4 t[kSliceLoads];
 #pragma unroll
@@ -1516,7 +1515,7 @@ static __global__ __launch_bounds__(kApplyThreads) void k_bloom_apply(uint32_t *
     __syncthreads();
     // merge: this workgroup is the only writer of its slice
     const uint64_t w0 = (uint64_t)b * slice_words;
-    const bool nt = (g.dbg & kGeomNtBit) != 0 && tab_words >= kNtTableWords;  // (see slice_piece)
+    const bool nt = tab_words >= kNtTableWords;  // (see slice_piece)
     typedef unsigned int nt_u32x4 __attribute__((ext_vector_type(4)));
     if (sm.on) {
         for (uint32_t w = threadIdx.x * 4; w < slice_words; w += kApplyThreads * 4) {
@@ -1607,7 +1606,7 @@ static __global__ __launch_bounds__(kApplyThreads) void k_bloom_test(const uint3
     const uint64_t w0 = (uint64_t)b * slice_words;
     const uint32_t dbg = kBenchKnobs ? g.dbg : 0u;
     const uint32_t mycnt = lane_segment_count(segcnt, g, b);  // (requested before the slice: see lane_segment_count)
-    if (!(dbg & 128)) load_slice(smem, tab, tab_words, w0, slice_words, (g.dbg & kGeomNtBit) != 0);
+    if (!(dbg & 128)) load_slice(smem, tab, tab_words, w0, slice_words);
     __syncthreads();
     const uint32_t kmask = (1u << (31 - g.shift)) - 1;
     for_each_batch_at<kApplyDepth>(buckets, segcnt, g, b, make_uint4(0, 0, 0, 0), [&](const uint4 (&q)[kApplyDepth], const uint64_t (&at)[kApplyDepth],
@@ -1685,7 +1684,7 @@ static __global__ __launch_bounds__(kApplyThreads) void k_bloom_test_flag(const 
     const uint32_t slice_words = 1u << (g.shift - 5);
     const uint64_t w0 = (uint64_t)b * slice_words;
     const uint32_t mycnt = lane_segment_count(segcnt, g, b);  // (requested before the slice: see lane_segment_count)
-    load_slice(smem, tab, tab_words, w0, slice_words, (g.dbg & kGeomNtBit) != 0);
+    load_slice(smem, tab, tab_words, w0, slice_words);
     __syncthreads();
     for_each_batch_at<kFlagDepth>(buckets, segcnt, g, b, make_uint4(0, 0, 0, 0), [&](const uint4 (&q)[kFlagDepth], const uint64_t (&)[kFlagDepth],
                                                                                    const uint32_t (&wg)[kFlagDepth]) {

@@ -9,18 +9,17 @@
 //   * pass 1 (k_part_scatter<..., PayNonePhased>) runs once over the window's key list; a tile never straddles two phases, and a
 //     (slice, workgroup) segment receives its tiles in order, so the end-of-phase fill counts (snap[phase][slice][workgroup]) cut
 //     every segment into per-phase pieces;
-//   * the fold (k_win_fold) keeps an image of the real counters of its table part in LDS -- four bits per counter (min(counter, 15)), a
-//     whole 2^18-counter slice per workgroup (default), or a byte per counter (min(counter, 255)), 2^17 counters, two workgroups per slice
-//     each applying the probes of its half -- and walks the slice's probes phase by phase: adds with a returning ds_add, barrier, removes
-//     with a returning ds_sub whose old value must be 1 .. 14 (1 .. 254).
+//   * the fold (k_win_fold) keeps an image of the real counters of its slice in LDS -- four bits per counter (min(counter, 15)), a
+//     whole slice of up to 2^18 counters per workgroup -- and walks the slice's probes phase by phase: adds with a returning ds_add,
+//     barrier, removes with a returning ds_sub whose old value must be 1 .. 14.
 //     With T[c] the counter before a remove phase and R[c] the phase's probes on it:  T[c] >= R[c] for every c, none frozen  ==>
 //     every key of the phase is removed whatever the order inside it (each of its counters holds >= 1 just before its own
 //     decrement), and the result is T - R.  By induction over the phases the window's result is the sequential one.
 //   * a remove that meets a zero (or a frozen / saturating counter) raises the window's flag: the host then UNDOES the fold
 //     (k_win_fold<true>: the inverse net delta, wrapping arithmetic, exact) and replays the window batch by batch through the
 //     validated per-batch path -- the reference's semantics for any stream, automatically.
-// Counters of 14 (254) and more do not fit the image's arithmetic: a part that touches one drops its image and applies its probes, phase
-// by phase, with wrapping atomics on the table itself (the part is its alone) -- same checks, exact.  The same for a (segment, phase) piece
+// Counters of 14 and more do not fit the image's arithmetic: a slice that touches one drops its image and applies its probes, phase
+// by phase, with wrapping atomics on the table itself (the slice is its alone) -- same checks, exact.  The same for a (segment, phase) piece
 // of more probe groups than the walk keeps in registers (12; 20 in the wide form that tables of few slices take).
 #pragma once
 #include "psk_nibble.hpp"
@@ -29,22 +28,15 @@
 
 namespace psk {
 
-constexpr uint32_t kWinPartShift = 17;  // log2(counters of one workgroup's BYTE image): 128 KiB
-constexpr uint32_t kWinNibShift = 18;   // ... of its NIBBLE image (round 4, second form): a whole 2^18-counter slice in 128 KiB
-__host__ __device__ __forceinline__ uint32_t win_part_shift(uint32_t slice_shift, bool nib)
-{
-    const uint32_t cap = nib ? kWinNibShift : kWinPartShift;
-    return slice_shift < cap ? slice_shift : cap;
-}
 constexpr int kWinMaxPhases = 192;   // (their 4-bit group counts sit next to the image: 192 x 128 bytes for 256 pass-1 workgroups)
 struct WinPhases {
     uint32_t nph;
     const PhaseDesc *ph;                // device table of pass 1 (ph[p].remove; uniform reads)
 };
-// what a fold workgroup did to its table part (status[blockIdx.x]); the undo inverts exactly that
+// what a fold workgroup did to its slice (status[blockIdx.x]); the undo inverts exactly that
 constexpr uint32_t kWinWritten = 0;   // image written back
 constexpr uint32_t kWinAborted = 1;   // a remove met a zero: nothing written
-constexpr uint32_t kWinAtomics = 2;   // applied with wrapping atomics on the table (a counter >= 254 in play)
+constexpr uint32_t kWinAtomics = 2;   // applied with wrapping atomics on the table (a counter >= 14 in play)
 
 // the six slice-local indices of a probe group that are valid (PayNone: two halves of 3 x 20 bits, valid count in bits 60..63)
 template <class F>
@@ -138,42 +130,36 @@ __device__ __forceinline__ void win_walk_simple(const PartGeom &g, const uint4 *
 
 // wide: five instead of three probe groups per lane and phase, whole bytes instead of nibbles for the per-(phase, segment) group counts --
 // tables of few slices, whose tiles bring long runs per slice (host's choice, psk_part_cbf_window.hip)
-static inline size_t win_fold_lds(const PartGeom &g, uint32_t nph, bool nib, bool wide = false)
+static inline size_t win_fold_lds(const PartGeom &g, uint32_t nph, bool wide = false)
 {
-    const uint32_t pshift = win_part_shift(g.shift, nib);
     const size_t row = wide ? g.nwg : (g.nwg + 1) / 2;
-    return ((size_t)1 << (nib ? pshift - 1 : pshift)) + (((size_t)nph * row + 3) & ~(size_t)3) + (((size_t)nph + 31) / 32) * 4 + 16;
+    return ((size_t)1 << (g.shift - 1)) + (((size_t)nph * row + 3) & ~(size_t)3) + (((size_t)nph + 31) / 32) * 4 + 16;
 }
 
-// UNDO = false: apply the window to my table part (blockIdx.x = slice * parts + part); flag: a remove met a zero / a counter
-// would freeze -- the window has to be undone and replayed.  UNDO = true: the exact inverse of what the forward launch did.
-// dynamic LDS: the byte image, 2^min(shift, 17) bytes | 4-bit group counts [phases][ceil(nwg / 2)] | phase types (win_fold_lds)
-// NIB (round 4): the image holds min(counter, 15) in four bits, so ONE workgroup takes a whole 2^18-counter slice and every probe group is
-// decoded once -- with byte images two workgroups per slice each decoded all of the slice's groups and applied half (the walk is bound by
-// that decoding).  Same proof: adds must meet 0 .. 13, removes 1 .. 14 (15 = a counter the image cannot follow: atomics on the table); a
-// nibble that carries or borrows into its neighbour has raised the taint / violation flag first, and either flag discards the image.
-template <bool UNDO, bool NIB, int RG = 3>
+// UNDO = false: apply the window to my slice (blockIdx.x; nib_geometry: at most 2^18 counters, a 128 KiB image); flag: a remove met a
+// zero / a counter would freeze -- the window has to be undone and replayed.  UNDO = true: the exact inverse of what the forward launch did.
+// dynamic LDS: the nibble image, 2^(shift - 1) bytes | 4-bit group counts [phases][ceil(nwg / 2)] | phase types (win_fold_lds)
+// The image holds min(counter, 15) in four bits, so ONE workgroup takes a whole slice and every probe group is decoded once (the walk is
+// bound by that decoding; a byte image, two workgroups per slice, measured slower: NOTES.md §9.1).  Adds must meet 0 .. 13, removes
+// 1 .. 14 (15 = a counter the image cannot follow: atomics on the table); a nibble that carries or borrows into its neighbour has raised
+// the taint / violation flag first, and either flag discards the image.
+// The table is read and written with nontemporal accesses (scripts/ubench/tabpass.hip: a pass over a table far larger than the
+// Infinity Cache runs 8-12 % faster with them, and the window's probe groups keep the cache).
+template <bool UNDO, int RG = 3>
 __global__ __launch_bounds__(kApplyThreads) void k_win_fold(uint32_t *tab, uint64_t tab_cells, PartGeom g, const uint4 *buckets, const uint32_t *snap,
-                                                            WinPhases wp, uint32_t *status, uint32_t *flag, uint32_t nt, uint32_t *shadow_out)
+                                                            WinPhases wp, uint32_t *status, uint32_t *flag)
 {
-    // shadow_out (forward fold with nibble images only; may be null): the kept 4-bit images of the lookups (psk_sketch::shadow) -- the fold
-    // ends with exactly that image of every slice in LDS, so the lookups that follow a flush need not read the table again.  flag[1] tells
-    // the host when a slice took the atomics instead (its image is void: the kept images are dropped).
-    // nt: nontemporal loads / stores of the table part (round 4; scripts/ubench/tabpass.hip: a pass over a table far larger than the
-    // Infinity Cache runs 8-12 % faster with them, and the window's probe groups keep the cache)
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     __shared__ uint32_t s_viol, s_taint;
-    const uint32_t pshift = win_part_shift(g.shift, NIB);
-    const uint32_t nparts = 1u << (g.shift - pshift);
-    const uint32_t b = blockIdx.x / nparts, h = blockIdx.x % nparts;
-    const uint32_t pieces = 1u << (pshift - 2);  // 16-byte pieces of my table part = words (bytes) / 16-bit halves (nibbles) of the image
-    const uint32_t img_words = NIB ? pieces / 2 : pieces;
-    constexpr uint32_t kTop = NIB ? 15u : 255u;   // the marker: a counter the image cannot follow
+    const uint32_t b = blockIdx.x;
+    const uint32_t pieces = 1u << (g.shift - 2);  // 16-byte pieces of my slice = 16-bit halves of the image
+    const uint32_t img_words = pieces / 2;
+    constexpr uint32_t kTop = 15u;   // the marker: a counter the image cannot follow
     uint16_t *half16 = reinterpret_cast<uint16_t *>(smem);
-    const uint32_t pmask = (1u << pshift) - 1;
-    const uint64_t c0 = ((uint64_t)b << g.shift) + ((uint64_t)h << pshift);
+    const uint32_t pmask = (1u << g.shift) - 1;
+    const uint64_t c0 = (uint64_t)b << g.shift;
     if (c0 >= tab_cells) {
-        if (!UNDO && threadIdx.x == 0) status[blockIdx.x] = kWinAborted;  // (a part past the table's end: nothing to do, nothing to undo)
+        if (!UNDO && threadIdx.x == 0) status[blockIdx.x] = kWinAborted;  // (a slice past the table's end: nothing to do, nothing to undo)
         return;
     }
     uint32_t st_fwd = kWinWritten;
@@ -185,8 +171,8 @@ __global__ __launch_bounds__(kApplyThreads) void k_win_fold(uint32_t *tab, uint6
     auto atomics_pass = [&](bool inverse) {
         uint32_t bad = 0;
         win_walk_simple(g, buckets, snap, wp, b, !inverse, [&](uint32_t x, bool rem) {
-            if ((x >> pshift) != h) return;
-            uint32_t *cell = tab + c0 + (x & pmask);
+            if ((x >> g.shift) != 0) return;  // (an index past the slice: not applied)
+            uint32_t *cell = tab + c0 + x;
             if (inverse) {
                 if (rem) atomicAdd(cell, 1u);
                 else atomicSub(cell, 1u);
@@ -204,7 +190,7 @@ __global__ __launch_bounds__(kApplyThreads) void k_win_fold(uint32_t *tab, uint6
         atomics_pass(true);
         return;
     }
-    // ---- my part of the table -> byte image (min(counter, 255); 255 marks a counter the image cannot follow)
+    // ---- my slice of the table -> nibble image (min(counter, 15); 15 marks a counter the image cannot follow)
     if (threadIdx.x == 0) s_viol = s_taint = 0;
     {
         constexpr int U = 8;
@@ -213,27 +199,23 @@ __global__ __launch_bounds__(kApplyThreads) void k_win_fold(uint32_t *tab, uint6
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const uint32_t pc = p0 + (uint32_t)u * kApplyThreads;
-                t[u] = pc < pieces ? nib_load_piece(tab, tab_cells, c0 + 4ULL * pc, nt != 0) : make_uint4(0, 0, 0, 0);
+                t[u] = pc < pieces ? nib_load_piece(tab, tab_cells, c0 + 4ULL * pc, true) : make_uint4(0, 0, 0, 0);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const uint32_t pc = p0 + (uint32_t)u * kApplyThreads;
-                auto by = [](uint32_t c) -> uint32_t { return c < 255u ? c : 255u; };
-                if (pc < pieces) {
-                    if (NIB) half16[pc] = (uint16_t)nib_pack4(t[u]);
-                    else smem[pc] = by(t[u].x) | (by(t[u].y) << 8) | (by(t[u].z) << 16) | (by(t[u].w) << 24);
-                }
+                if (pc < pieces) half16[pc] = (uint16_t)nib_pack4(t[u]);
             }
         }
     }
     __syncthreads();
     if (UNDO) {
-        // the inverse net delta, in any order: word arithmetic modulo 2^32 -- carries between the bytes cancel, every byte ends
-        // where it started (all of them were below 255 when the forward launch wrote them)
+        // the inverse net delta, in any order: word arithmetic modulo 2^32 -- carries between the nibbles cancel, every nibble ends
+        // where it started (all of them were below 15 when the forward launch wrote them)
         win_walk_simple(g, buckets, snap, wp, b, false, [&](uint32_t x, bool rem) {
-            if ((x >> pshift) != h) return;
-            const uint32_t c = x & pmask, one = NIB ? 1u << ((c & 7u) * 4u) : 1u << ((c & 3u) * 8u);
-            uint32_t *word = &smem[NIB ? c >> 3 : c >> 2];
+            if ((x >> g.shift) != 0) return;
+            const uint32_t one = 1u << ((x & 7u) * 4u);
+            uint32_t *word = &smem[x >> 3];
             if (rem) atomicAdd(word, one);
             else atomicSub(word, one);
         });
@@ -282,30 +264,29 @@ __global__ __launch_bounds__(kApplyThreads) void k_win_fold(uint32_t *tab, uint6
             const uint32_t d = WIDE ? (uint32_t)cnt4[p * row + wl.seg] : (cnt4[p * row + (wl.seg >> 1)] >> (4 * (wl.seg & 1))) & 15u;
             return d;
         };
-        // one probe group: the returning LDS atomics of its probes (mine: valid slot, my half of the slice) issue back to back, then the
-        // old bytes are judged.  rm: all ones in a remove phase, else 0.  The atomics run under the lane's own predicate: the LDS pipe
-        // is what bounds a phase (~3 lanes per clock and CU for random returning atomics), so a probe of the other half must not cost
+        // one probe group: the returning LDS atomics of its probes (mine: a valid slot inside the slice) issue back to back, then the
+        // old nibbles are judged.  rm: all ones in a remove phase, else 0.  The atomics run under the lane's own predicate: the LDS pipe
+        // is what bounds a phase (~3 lanes per clock and CU for random returning atomics), so a probe that is not applied must not cost
         // a slot -- a fully branch-free version that added 0 for those took 3.3 us per phase, as long as the waits it replaced.
         // (per group: ~12 VALU per probe -- the fold is bound by VALU issue, 4 cycles per wave64 instruction with four waves per SIMD,
         // not by its waits: three applies per lane and phase at ~130 instructions each were 2.7 us per phase)
-        const uint32_t amask = pmask & ~3u;          // byte address of the counter's word in the byte image
-        const uint32_t hmask = (1u << (20 - pshift)) - 1u;  // which part of the slice a 20-bit index belongs to
+        const uint32_t hmask = (1u << (20 - g.shift)) - 1u;  // the bits of a 20-bit index above the slice
         auto apply = [&](const win_u32x4 &q, uint32_t rm) {
             const uint32_t n0 = q.y >> 28, n1 = q.w >> 28;
             const uint32_t x[6] = {q.x, __builtin_amdgcn_alignbit(q.y, q.x, 20), q.y >> 8, q.z, __builtin_amdgcn_alignbit(q.w, q.z, 20), q.w >> 8};
-            const uint32_t pm = rm | 1u;             // +1 (adds) or -1 (removes): shifted into the counter's byte lane
+            const uint32_t pm = rm | 1u;             // +1 (adds) or -1 (removes): shifted into the counter's nibble
             uint32_t ob[6];
 #pragma unroll
             for (int e = 0; e < 6; ++e) {
-                const bool mine = (uint32_t)(e % 3) < (e < 3 ? n0 : n1) && ((x[e] >> pshift) & hmask) == h;
-                const uint32_t sh = NIB ? (x[e] & 7u) * 4u : (x[e] & 3u) * 8u;
-                const uint32_t waddr = NIB ? ((x[e] & pmask) >> 1) & ~3u : x[e] & amask;  // byte address of the counter's image word
-                uint32_t old = NIB ? 0x11111111u : 0x01010101u;  // (a probe that is not mine: an old value nobody objects to)
+                const bool mine = (uint32_t)(e % 3) < (e < 3 ? n0 : n1) && ((x[e] >> g.shift) & hmask) == 0;
+                const uint32_t sh = (x[e] & 7u) * 4u;
+                const uint32_t waddr = ((x[e] & pmask) >> 1) & ~3u;  // byte address of the counter's image word
+                uint32_t old = 0x11111111u;  // (a probe that is not mine: an old value nobody objects to)
                 if (mine) old = atomicAdd(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(smem) + waddr), pm << sh);  // ds_add_rtn_u32
                 ob[e] = (old >> sh) & kTop;
             }
-            // removes: every old byte must be 1 .. 254 (0: the key is not there -- countingbloom.py:200-201; 255: beyond the image);
-            // adds: 0 .. 253 (254 would become the marker)
+            // removes: every old nibble must be 1 .. 14 (0: the key is not there -- countingbloom.py:200-201; 15: beyond the image);
+            // adds: 0 .. 13 (14 would become the marker)
             const uint32_t mn = min(min(min(ob[0], ob[1]), min(ob[2], ob[3])), min(ob[4], ob[5]));
             const uint32_t mx = max(max(max(ob[0], ob[1]), max(ob[2], ob[3])), max(ob[4], ob[5]));
             viol |= rm & (uint32_t)(mn == 0u);
@@ -353,40 +334,12 @@ __global__ __launch_bounds__(kApplyThreads) void k_win_fold(uint32_t *tab, uint6
         if (viol) s_viol = 1u;
         if (taint) s_taint = 1u;
         __syncthreads();
-        if (s_taint) {  // a counter of 254 or more in play: the image is void (bytes may have carried); the table part is still untouched
-            if (threadIdx.x == 0) {
-                status[blockIdx.x] = kWinAtomics;
-                flag[1] = 1u;  // (a tally for tests: slices that took the atomics)
-            }
+        if (s_taint) {  // a counter of 14 or more in play: the image is void (nibbles may have carried); the slice is still untouched
+            if (threadIdx.x == 0) status[blockIdx.x] = kWinAtomics;
             atomics_pass(false);
-            if constexpr (NIB) {
-                if (shadow_out) {
-                    // the kept image of this slice from the table itself, now that the atomics are through: every lane's atomics have
-                    // returned (they are returning ones), the barrier collects the workgroup, and the loads go past this CU's L1, which
-                    // still holds the lines of the first load
-                    __threadfence();
-                    __syncthreads();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    uint16_t *dst = reinterpret_cast<uint16_t *>(shadow_out + (uint64_t)blockIdx.x * img_words);
-                    constexpr int U = 8;
-                    for (uint32_t p0 = threadIdx.x; p0 < pieces; p0 += kApplyThreads * U) {
-                        uint4 t[U];
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            const uint32_t pc = p0 + (uint32_t)u * kApplyThreads;
-                            t[u] = pc < pieces ? nib_load_piece(tab, tab_cells, c0 + 4ULL * pc, true) : make_uint4(0, 0, 0, 0);
-                        }
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            const uint32_t pc = p0 + (uint32_t)u * kApplyThreads;
-                            if (pc < pieces) dst[pc] = (uint16_t)nib_pack4(t[u]);
-                        }
-                    }
-                }
-            }
             return;
         }
-        if (s_viol) {  // a remove met a zero: nothing of this part reaches the table; the host undoes the others and replays the window
+        if (s_viol) {  // a remove met a zero: nothing of this slice reaches the table; the host undoes the others and replays the window
             if (threadIdx.x == 0) {
                 status[blockIdx.x] = kWinAborted;
                 *flag = 1u;
@@ -395,37 +348,20 @@ __global__ __launch_bounds__(kApplyThreads) void k_win_fold(uint32_t *tab, uint6
         }
         if (threadIdx.x == 0) status[blockIdx.x] = kWinWritten;
     }
-    // ---- image -> table (a value of 255 / 15 is a counter nobody touched: it keeps its value)
+    // ---- image -> table (a value of 15 is a counter nobody touched: it keeps its value)
     for (uint32_t pc = threadIdx.x; pc < pieces; pc += kApplyThreads) {
         const uint64_t gc = c0 + 4ULL * pc;
-        uint32_t v[4];
-        if (NIB) {
-            const uint32_t w = half16[pc];
-            v[0] = w & 15u; v[1] = (w >> 4) & 15u; v[2] = (w >> 8) & 15u; v[3] = w >> 12;
-        } else {
-            const uint32_t w = smem[pc];
-            v[0] = w & 255u; v[1] = (w >> 8) & 255u; v[2] = (w >> 16) & 255u; v[3] = w >> 24;
-        }
+        const uint32_t w = half16[pc];
+        const uint32_t v[4] = {w & 15u, (w >> 4) & 15u, (w >> 8) & 15u, w >> 12};
         const bool marked = v[0] == kTop || v[1] == kTop || v[2] == kTop || v[3] == kTop;
         if (!marked && gc + 3 < tab_cells) {
-            if (nt) {
-                psk_u32x4 o;
-                o.x = v[0]; o.y = v[1]; o.z = v[2]; o.w = v[3];
-                __builtin_nontemporal_store(o, reinterpret_cast<psk_u32x4 *>(tab + gc));
-            } else {
-                *reinterpret_cast<uint4 *>(tab + gc) = make_uint4(v[0], v[1], v[2], v[3]);
-            }
+            psk_u32x4 o;
+            o.x = v[0]; o.y = v[1]; o.z = v[2]; o.w = v[3];
+            __builtin_nontemporal_store(o, reinterpret_cast<psk_u32x4 *>(tab + gc));
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (v[e] != kTop && gc + e < tab_cells) tab[gc + e] = v[e];
-        }
-    }
-    if constexpr (NIB && !UNDO) {
-        if (shadow_out) {  // (nparts == 1: blockIdx.x is the slice; the image is read-only from here on)
-            uint4 *dst = reinterpret_cast<uint4 *>(shadow_out + (uint64_t)blockIdx.x * img_words);
-            const uint4 *src = reinterpret_cast<const uint4 *>(smem);
-            for (uint32_t v = threadIdx.x; v < img_words / 4; v += kApplyThreads) dst[v] = src[v];
         }
     }
 }

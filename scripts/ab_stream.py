@@ -1,4 +1,4 @@
-"""round 3: cost of enqueueing inserts on a non-default stream (ab_overlap.py showed two-stream inserts 3.5x slower than serial)"""
+"""round 3: cost of enqueueing inserts on a non-default stream (a first two-stream A/B had shown inserts 3.5x slower than serial)"""
 import sys, time
 import numpy as np, torch
 sys.path.insert(0, ".")

@@ -74,15 +74,16 @@ def test_fails_loudly_without_a_device():
 SUPPORTED_OPTIONS = ["partition", "partition_min_keys", "partition_max_keys", "partition_cache_bytes", "scratch_budget_bytes", "pass1_bins", "bloom_lookup",
                      "cms_small_weights", "cbf_lookup_shadow", "remove_exact", "update_window", "update_window_keys", "auto_combine", "combine_keys",
                      "merge_single_rank"]
-# A/B switches of experiments that were measured and dropped: bench build (-DPSK_BENCH_KNOBS=1) only
+# A/B switches of experiments that were measured and dropped, and removed with the code they selected: no build knows them
 RETIRED_OPTIONS = ["update_window_shadow", "update_window_image", "update_window_nt", "nibble_lookup_pipe", "nibble_update_pipe", "nibble_update_parts",
                    "nibble_update_layout", "nibble_nt_loads", "big_table_nt", "lookup_split", "lookup_run_lanes", "lookup_collect_threads", "slice_bias",
-                   "scatter_workgroups", "combine_scatter", "combine_fused_flush", "part_debug"]
+                   "scatter_workgroups", "combine_scatter", "combine_fused_flush"]
 
 
 def test_option_table_supported_names_work_and_retired_ones_are_rejected():
-    """psk_set_option / psk_get_option are host-only: the shipped library knows every name of include/psk.h's table, gives each back what was
-    set, and answers "unknown option" to the retired bench knobs"""
+    """psk_set_option / psk_get_option are host-only: the library knows every name of include/psk.h's table, gives each back what was
+    set, and answers "unknown option" to the retired A/B switches; the measuring tools' "part_debug" exists in the bench
+    build (-DPSK_BENCH_KNOBS=1, libpsk_hip_knobs.so) only"""
     from pyprobables_amd import _native as N
 
     L = N.lib()
@@ -93,10 +94,13 @@ def test_option_table_supported_names_work_and_retired_ones_are_rejected():
         old = N.get_option(name)
         N.set_option(name, old)
         assert N.get_option(name) == old
-    if N.LIB_PATH.name != "libpsk_hip.so":
-        return  # (a bench build loaded through PSK_LIB_PATH knows the retired names by design)
+    v = C.c_int64(0)
     for name in RETIRED_OPTIONS:
         assert L.psk_set_option(name.encode(), 0) != 0 and "unknown option" in N.last_error(), name
-        v = C.c_int64(0)
         assert L.psk_get_option(name.encode(), C.byref(v)) != 0, name
+    if N.LIB_PATH.name == "libpsk_hip_knobs.so":
+        assert L.psk_set_option(b"part_debug", 0) == 0 and L.psk_get_option(b"part_debug", C.byref(v)) == 0 and v.value == 0
+    else:
+        assert L.psk_set_option(b"part_debug", 0) != 0 and "unknown option" in N.last_error()
+        assert L.psk_get_option(b"part_debug", C.byref(v)) != 0
     assert L.psk_set_option(b"update_window_folds", 1) != 0 and "read-only" in N.last_error()  # counters are read-only

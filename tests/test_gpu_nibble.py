@@ -208,24 +208,29 @@ def test_small_add_batches_into_a_big_table_are_write_combined_automatically(pa,
         N.set_option("auto_combine", 1)
 
 
-def test_opt_in_combining_mixes_scattered_and_key_lists(pa, oracle, request):
-    """combine_updates=True: unit-weight batches wait as scattered probes, weighted ones as key lists; at the flush all adds
-    of both land before all removes of both (well-formed stream)"""
+def test_opt_in_combining_mixes_scattered_and_key_lists(pa, oracle):
+    """psk_cbf_add (update windows off) holds small unit-weight adds as scattered probes, psk_cbf_update_combined holds key lists on the
+    SAME handle; at the flush all adds of both land before all removes of both (well-formed stream: the key-list removes take keys whose
+    adds wait as scattered probes)"""
     from pyprobables_amd import _native as N
 
-    B = 300_000
-    from _util import knob
-
-    knob("combine_scatter", 1)   # (off by default: measured slower on BASELINE cfg 4's 1 M-key batches; bench build only)
-    request.addfinalizer(lambda: N.set_option("combine_scatter", 0))
-    cbf = pa.CountingBloomFilter(est_elements=28005615, false_positive_rate=0.01, combine_updates=True)
+    B = 600_000                                           # (k = 7: at least 2^19 keys for a scattered add, fewer than cells / 8 probes)
+    cbf = pa.CountingBloomFilter(est_elements=28005615, false_positive_rate=0.01)
+    cbf.set_engine_option("update_window", 0)
     oc = oracle.OracleCBF(2**28, 7)
     k0, k1, k2 = (oracle.gen_keys16(i * B, B) for i in range(3))
     w = (np.arange(B, dtype=np.int64) % 3) + 1
-    cbf.add_many(_dev(k0))                                # scattered
-    cbf.add_many(_dev(k1), w.astype(np.uint32))           # key list (weighted)
-    cbf.remove_many(_dev(k0[: B // 2]))                   # scattered decrement
-    cbf.remove_many(_dev(k1[: B // 2]), w[: B // 2].astype(np.uint32))  # key list
+    d0, d1, dw = _dev(k0), _dev(k1), _dev(w.astype(np.uint32))
+    L, h, st = N.lib(), cbf._tab.handle, cbf._tab.stream
+
+    def combined(d, n, w_addr, remove):
+        N.check(L.psk_cbf_update_combined(h, N.KEYS_FIXED, d.data_ptr(), None, n, 16, w_addr, remove, N.DEVICE, st))
+
+    cbf.add_many(d0)                                      # scattered
+    assert cbf.scratch_bytes()["waiting_updates"] > 0
+    combined(d1, B, dw.data_ptr(), 0)                     # key list (weighted)
+    combined(d0, B // 2, None, 1)                         # key list: removes of keys whose adds wait scattered
+    combined(d1, B // 2, dw.data_ptr(), 1)                # key list (weighted)
     cbf.add_many(_dev(k2))
     oc.update_keys(k0)
     oc.update_keys(k1, w)
@@ -475,46 +480,32 @@ def test_repeated_lookups_keep_the_4bit_images_until_the_table_changes(pa, oracl
         N.set_option("cbf_lookup_shadow", 1)
 
 
-@pytest.mark.parametrize("update_pipe,lookup_pipe", [(1, 0), (3, 1), (0, 1), (0, 0)])
 @pytest.mark.parametrize("est", [28005615, 10_000_000])
-def test_pipelined_table_passes_and_their_ab_partners_agree_with_the_oracle(pa, oracle, force_partition, est, update_pipe, lookup_pipe):
-    """Round 4: k_nib_apply_pipe (persistent workgroups, the fold of one slice under the probe groups of the next; options 1 =
-    nontemporal, 3 = plain table accesses) and k_nib_gather_pipe (option `nibble_lookup_pipe`), against k_nib_apply / k_nib_gather
-    (0) and the oracle: unit adds with a key repeated 41 times (its slices overflow their 4-bit deltas: exact atomics, and the slice
+def test_pipelined_table_passes_agree_with_the_oracle(pa, oracle, force_partition, est):
+    """Round 4: k_nib_apply_pipe (persistent workgroups, the fold of one slice under the probe groups of the next) and k_nib_gather
+    against the oracle: unit adds with a key repeated 41 times (its slices overflow their 4-bit deltas: exact atomics, and the slice
     behind them goes in unpipelined), the optimistic decrement, its undo + exact path, lookups.  est = 10 M: 9.6e7 counters, Barrett,
     the table ends inside the last slice.  countingbloom.py:135-208."""
-    from _util import knob, knob_value
-
-    N = force_partition
-    old = (knob_value("nibble_update_pipe", 1), knob_value("nibble_lookup_pipe", 0))
-    if (update_pipe, lookup_pipe) != (1, 0):  # (the A/B partners exist in the bench build only; the shipped library runs (1, 0))
-        knob("nibble_update_pipe", update_pipe)
-        knob("nibble_lookup_pipe", lookup_pipe)
-    try:
-        cbf = pa.CountingBloomFilter(est_elements=est, false_positive_rate=0.01)
-        m, k = cbf.number_bits, cbf.number_hashes
-        n = max(2_400_000, m // (8 * k) + 200_000)   # more than cells / 8 probes: the pass over the table
-        oc = oracle.OracleCBF(m, k)
-        keys = oracle.gen_keys16(11, n)
-        keys[2000:2040] = keys[9]
-        cbf.add_many(_dev(keys))
-        oc.update_keys(keys)
-        assert np.array_equal(_table(cbf), oc.bloom), "unit add"
-        present = keys[2100 : n - 100_000]
-        cbf.remove_many(_dev(present))
-        oc.update_keys(present, -np.ones(present.shape[0], dtype=np.int64))
-        assert np.array_equal(_table(cbf), oc.bloom), "optimistic decrement"
-        absent = oracle.gen_keys16(700_000_000, n)
-        absent = absent[oc.check_keys(absent) == 0]
-        rm = np.concatenate([keys[n - 100_000 :], absent])
-        cbf.remove_many(_dev(rm))
-        oc.update_keys(rm, -np.ones(rm.shape[0], dtype=np.int64))
-        assert np.array_equal(_table(cbf), oc.bloom), "decrement undone, exact path"
-        assert cbf.elements_added == oc.els_added
-        probe = np.concatenate([keys[:400_000], absent[:400_000], keys[n - 400_000 :]])
-        for _ in range(2):  # (the second lookup of an unchanged table may load kept images: k_nib_gather either way)
-            assert np.array_equal(cbf.check_many(_dev(probe)).cpu().numpy().astype(np.uint32), oc.check_keys(probe))
-    finally:
-        if (update_pipe, lookup_pipe) != (1, 0):
-            N.set_option("nibble_update_pipe", old[0])
-            N.set_option("nibble_lookup_pipe", old[1])
+    cbf = pa.CountingBloomFilter(est_elements=est, false_positive_rate=0.01)
+    m, k = cbf.number_bits, cbf.number_hashes
+    n = max(2_400_000, m // (8 * k) + 200_000)   # more than cells / 8 probes: the pass over the table
+    oc = oracle.OracleCBF(m, k)
+    keys = oracle.gen_keys16(11, n)
+    keys[2000:2040] = keys[9]
+    cbf.add_many(_dev(keys))
+    oc.update_keys(keys)
+    assert np.array_equal(_table(cbf), oc.bloom), "unit add"
+    present = keys[2100 : n - 100_000]
+    cbf.remove_many(_dev(present))
+    oc.update_keys(present, -np.ones(present.shape[0], dtype=np.int64))
+    assert np.array_equal(_table(cbf), oc.bloom), "optimistic decrement"
+    absent = oracle.gen_keys16(700_000_000, n)
+    absent = absent[oc.check_keys(absent) == 0]
+    rm = np.concatenate([keys[n - 100_000 :], absent])
+    cbf.remove_many(_dev(rm))
+    oc.update_keys(rm, -np.ones(rm.shape[0], dtype=np.int64))
+    assert np.array_equal(_table(cbf), oc.bloom), "decrement undone, exact path"
+    assert cbf.elements_added == oc.els_added
+    probe = np.concatenate([keys[:400_000], absent[:400_000], keys[n - 400_000 :]])
+    for _ in range(2):  # (the second lookup of an unchanged table may load kept images: k_nib_gather either way)
+        assert np.array_equal(cbf.check_many(_dev(probe)).cpu().numpy().astype(np.uint32), oc.check_keys(probe))

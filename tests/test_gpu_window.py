@@ -21,28 +21,21 @@ def pa():
     return pyprobables_amd
 
 
-@pytest.fixture(params=[4, 8], ids=["nibble-image", "byte-image"])
-def N(request):
-    """every case runs under both forms of the fold's LDS image (option update_window_image): 4 bits per counter, one workgroup per
-    2^18-counter slice (default), and 8 bits, two workgroups per slice"""
+@pytest.fixture(params=["nibble-image"])
+def N():
+    """the fold's LDS image holds 4 bits per counter, one workgroup per slice (the param names the form in every test id)"""
     from pyprobables_amd import _native as N
 
     import gc
-
-    from _util import knob
 
     # the fold / replay counters the tests read are PROCESS-wide: a sketch of an earlier test that is collected in the middle of this one
     # flushes its waiting window in psk_destroy and is counted here -- collect what is garbage first
     gc.collect()
     names = ("update_window", "update_window_keys", "update_window_force_fail")
     old = [N.get_option(k) for k in names]
-    if request.param != 4:
-        knob("update_window_image", request.param)  # (the byte-image fold is the round-4 A/B partner: bench build only)
     yield N
     for k, v in zip(names, old):
         N.set_option(k, v)
-    if request.param != 4:
-        N.set_option("update_window_image", 4)
 
 
 def _dev(a):
@@ -81,7 +74,7 @@ def _same(cbf, oc):
 
 @pytest.mark.parametrize("est", [3_600_000, 10_000_000])
 def test_mixed_stream_is_folded_in_one_pass_and_matches_the_oracle(pa, oracle, N, est):
-    """3.45e7 counters (132 slices of 2^18: two fold workgroups per slice) and 9.6e7 (Barrett indices)"""
+    """3.45e7 counters (132 slices of 2^18) and 9.6e7 (Barrett indices)"""
     cbf = pa.CountingBloomFilter(est_elements=est, false_positive_rate=0.01)
     m, k = cbf.number_bits, cbf.number_hashes
     assert m > 2**24
@@ -166,8 +159,9 @@ def test_forced_failure_undoes_exactly(pa, oracle, N):
     assert N.get_option("update_window_replays") == replays + 1
 
 
-def test_counters_beyond_the_byte_image_take_the_atomics(pa, oracle, N):
-    """a part that meets a counter of 254 or more drops its image and applies its probes to the table itself -- exact"""
+def test_big_and_frozen_counters_take_the_atomics(pa, oracle, N):
+    """a slice that meets a counter the image cannot follow (1000 and more, frozen ones) drops its image and applies its probes to the
+    table itself -- exact"""
     cbf = pa.CountingBloomFilter(est_elements=3_600_000, false_positive_rate=0.01)
     m, k = cbf.number_bits, cbf.number_hashes
     oc = oracle.OracleCBF(m, k)
@@ -238,46 +232,6 @@ def test_counters_around_the_nibble_image_limit(pa, oracle, N):
     ops2 = [(True, hot), (False, base[200_000:260_000]), (True, hot), (True, base[200_000:230_000])]
     _run(cbf, oc, ops2)
     _same(cbf, oc)
-
-
-def test_a_fold_leaves_the_lookups_kept_images_up_to_date(pa, oracle, N):
-    """lookups of a big table keep 4-bit slice images while it does not change (psk_sketch::shadow); a window fold with nibble images ends
-    with exactly those images in LDS and writes them back, so the lookup behind the flush loads them instead of reading the table again --
-    and must answer exactly (countingbloom.py:166-174) for present, removed and absent keys.  The byte-image fold leaves them stale.
-    (Option update_window_shadow; off by default -- the saving measured within the noise of a round of updates + lookups.)"""
-    cbf = pa.CountingBloomFilter(est_elements=20_000_000, false_positive_rate=0.01)   # 1.9e8 counters, 732 slices: runs short enough for the image path
-    m, k = cbf.number_bits, cbf.number_hashes
-    oc = oracle.OracleCBF(m, k)
-    _run(cbf, oc, _stream(oracle, 6, 200_000, seed=91))
-    probe = np.concatenate([oracle.gen_keys16(91, 500_000), oracle.gen_keys16(999_000_000, 200_000)])
-    dp = _dev(probe)
-    from _util import knob, knob_value
-
-    old = N.get_option("lookup_nibble_slices")
-    old_sh = knob_value("update_window_shadow", 0)
-    knob("update_window_shadow", 1)  # (off by default: measured without gain; bench build only)
-    N.set_option("lookup_nibble_slices", 2)  # (the 4-bit lookup path whatever the batch size)
-    try:
-        for _ in range(3):  # plain, build the images, load them
-            assert np.array_equal(cbf.check_many(dp).cpu().numpy().astype(np.uint32), oc.check_keys(probe))
-        hits, writes = N.get_option("cbf_lookup_shadow_hits"), N.get_option("update_window_shadow_writes")
-        folds = N.get_option("update_window_folds")
-        for rnd in range(3):
-            ops = _stream(oracle, 12, 400_000, seed=120 + rnd)     # fresh keys: adds + removes of half of them; 7 M operations: one window, one fold
-            _run(cbf, oc, ops)
-            got = cbf.check_many(dp).cpu().numpy().astype(np.uint32)   # the flush folds the window, then the lookup runs
-            assert np.array_equal(got, oc.check_keys(probe))
-            more = np.concatenate([ops[0][1][:50_000], ops[2][1][:50_000]])  # keys of this window: removed ones and live ones
-            assert np.array_equal(cbf.check_many(_dev(more)).cpu().numpy().astype(np.uint32), oc.check_keys(more))
-        assert N.get_option("update_window_folds") == folds + 3
-        nib = knob_value("update_window_image", 4) != 8
-        assert N.get_option("update_window_shadow_writes") - writes == (3 if nib else 0)
-        if nib:
-            assert N.get_option("cbf_lookup_shadow_hits") - hits >= 3   # the lookup behind every fold loaded the images it left
-        _same(cbf, oc)
-    finally:
-        N.set_option("lookup_nibble_slices", old)
-        N.set_option("update_window_shadow", old_sh)
 
 
 def test_combined_update_after_window_batches_keeps_the_order(pa, oracle, N):
