@@ -8,6 +8,7 @@
 #include <chrono>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 
 // ------------------------------------------------------------------ errors
@@ -66,15 +67,6 @@ int ensure(DevBuf &b, uint64_t bytes)
     return PSK_OK;
 }
 
-
-static int grid_for(uint64_t n)
-{
-    uint64_t g = (n + kBlock - 1) / kBlock;
-    const uint64_t cap = 256ULL * 16;  // 256 CUs x 16 blocks: grid-stride beyond that
-    if (g > cap) g = cap;
-    if (g == 0) g = 1;
-    return (int)g;
-}
 
 static int create_common(int kind, uint64_t m, uint32_t k, uint64_t padded, uint64_t logical, int device,
                          void *ext_table, psk_sketch **out)
@@ -143,6 +135,18 @@ extern "C" int psk_cms_create(uint64_t width, uint32_t depth, int device, void *
                          device, ext_table, out);
 }
 
+// Every scratch buffer of a handle, each ONCE: f(buffer, waiting) -> PSK_OK to go on.  waiting: the buffer holds updates that have not reached the
+// table (psk_scratch_bytes reports those apart).  psk_destroy, psk_scratch_bytes and psk_release_scratch all walk this one list.
+template <class F>
+static int for_each_scratch(psk_sketch *s, F &&f)
+{
+    for (DevBuf *b : {&s->s_keys, &s->s_offs, &s->s_w, &s->s_out, &s->s_aux, &s->s_part, &s->s_cnt, &s->s_flag, &s->s_spill, &s->s_tflag, &s->s_part2, &s->s_cnt2, &s->s_merge, &s->s_vals, &s->s_perm, &s->s_run, &s->s_tally,
+                      &s->s_brw, &s->shadow.img, &s->s_wstat, &s->s_phase})
+        PSK_TRY(f(*b, false));
+    for (DevBuf *b : {&s->comb.add.keys, &s->comb.add.w, &s->comb.rem.keys, &s->comb.rem.w, &s->scat.add.part, &s->scat.add.cnt, &s->win.keys, &s->s_snap}) PSK_TRY(f(*b, true));
+    return PSK_OK;
+}
+
 static inline void ho_apply(const psk_sketch *s);  // (the handle's option overrides -> this thread's effective values; defined with the options below)
 extern "C" int psk_destroy(psk_sketch *s)
 {
@@ -158,12 +162,11 @@ extern "C" int psk_destroy(psk_sketch *s)
     if (s->lk.dev) hipFree(s->lk.dev);
     if (s->lk.pin) hipHostFree((void *)s->lk.pin);
     if (s->wt.pin) hipHostFree((void *)s->wt.pin);
-    for (DevBuf *b : {&s->s_keys, &s->s_offs, &s->s_w, &s->s_out, &s->s_aux, &s->s_part, &s->s_cnt, &s->s_flag, &s->s_spill, &s->s_tflag, &s->s_part2, &s->s_cnt2, &s->s_merge, &s->s_vals, &s->s_perm, &s->s_run, &s->s_tally,
-                      &s->comb.add.keys, &s->comb.add.w, &s->comb.rem.keys, &s->comb.rem.w, &s->scat.add.part, &s->scat.add.cnt, &s->scat.rem.part, &s->scat.rem.cnt, &s->s_brw, &s->shadow.img,
-                      &s->win.keys, &s->s_snap, &s->s_wstat, &s->s_phase}) {
-        if (b->p) hipFree(b->p);
-        if (b->pin) hipHostFree(b->pin);
-    }
+    (void)for_each_scratch(s, [](DevBuf &b, bool) {
+        if (b.p) hipFree(b.p);
+        if (b.pin) hipHostFree(b.pin);
+        return (int)PSK_OK;
+    });
     if (s->win.pin) hipHostFree(s->win.pin);
     if (s->mbox) hipHostFree((void *)s->mbox);
     if (s->scat.ev) hipEventDestroy(s->scat.ev);
@@ -233,6 +236,18 @@ static __global__ __launch_bounds__(kBlock) void k_clear(uint4 *tab, uint64_t nv
 
 static int scat_drop(psk_sketch *s, hipStream_t st);  // forget the scattered write-combined updates (defined with them below)
 
+// forget every update that waits: the table is cleared or replaced, what has not reached it goes with the old contents
+static int drop_pending(psk_sketch *s, hipStream_t st)
+{
+    s->comb.add.n = s->comb.rem.n = 0;
+    s->comb.add.unit = s->comb.rem.unit = true;
+    s->comb.badd.clear();
+    s->comb.brem.clear();
+    s->win.n = s->win.copied = 0;  // (the update window too; a window's back-off is a property of the stream and stays)
+    s->win.batches.clear();
+    return scat_drop(s, st);
+}
+
 int64_t g_lazy_clear = 1;  // psk_set_option("lazy_clear", 0): every psk_clear sweeps the table at once (A/B of the deferred clear)
 
 // one launch for the table AND the counter block (two fills are two ~5 us launches; clear sits in every bench step)
@@ -258,13 +273,7 @@ extern "C" int psk_clear(psk_sketch *s, void *stream)
 {
     CHECK_HANDLE(s, -1);
     hipStream_t st = (hipStream_t)stream;
-    s->comb.add.n = s->comb.rem.n = 0;  // write-combined updates that have not reached the table are cleared with it
-    s->comb.add.unit = s->comb.rem.unit = true;
-    s->comb.badd.clear();
-    s->comb.brem.clear();
-    s->win.n = s->win.copied = 0;  // (the update window too; a window's back-off is a property of the stream and stays)
-    s->win.batches.clear();
-    PSK_TRY(scat_drop(s, st));
+    PSK_TRY(drop_pending(s, st));  // write-combined updates that have not reached the table are cleared with it
     // Bloom table that nobody outside the engine reads: the sweep is deferred.  The next entry point that reads, writes or hands out the
     // table runs it first on its own stream (clear_materialize), except a single-level partitioned insert, whose first apply STORES its
     // slices instead of read-modify-writing them (psk_part_bloom_add.hip): the 32 MiB of zeros are then neither written nor read back.
@@ -315,13 +324,7 @@ extern "C" int psk_write_table(psk_sketch *s, const void *src_host, uint64_t nby
     CHECK_HANDLE(s, -1);
     if (!src_host || nbytes > s->padded_bytes) return fail(PSK_EINVAL, "bad write_table arguments");
     hipStream_t st = (hipStream_t)stream;
-    s->comb.add.n = s->comb.rem.n = 0;  // the table is replaced: pending updates go with the old contents
-    s->comb.add.unit = s->comb.rem.unit = true;
-    s->comb.badd.clear();
-    s->comb.brem.clear();
-    s->win.n = s->win.copied = 0;
-    s->win.batches.clear();
-    PSK_TRY(scat_drop(s, st));
+    PSK_TRY(drop_pending(s, st));  // the table is replaced: pending updates go with the old contents
     s->clear_pending = false;  // (the fills below do what the deferred clear would)
     HIP_TRY(hipMemsetAsync(s->table, 0, s->padded_bytes, st));
     HIP_TRY(hipMemcpyAsync(s->table, src_host, nbytes, hipMemcpyHostToDevice, st));
@@ -329,7 +332,7 @@ extern "C" int psk_write_table(psk_sketch *s, const void *src_host, uint64_t nby
     if (s->kind != PSK_KIND_BLOOM) {
         // re-seed the wrap-free bound from the loaded counters
         const uint64_t nel = s->logical_bytes / 4;
-        hipLaunchKernelGGL(k_absmax, dim3(grid_for(nel)), dim3(kBlock), 0, st, (const uint32_t *)s->table, nel,
+        hipLaunchKernelGGL(k_absmax, dim3(grid_for_keys(nel)), dim3(kBlock), 0, st, (const uint32_t *)s->table, nel,
                            s->kind == PSK_KIND_CMS ? 1 : 0, s->ctr);
         HIP_TRY(hipGetLastError());
     }
@@ -348,7 +351,7 @@ extern "C" int psk_rescan_bound(psk_sketch *s, void *stream)
     PSK_TRY(flush_combined(s, st));
     HIP_TRY(hipMemsetAsync(s->ctr + PSK_CTR_ABS_BOUND, 0, sizeof(long long), st));
     const uint64_t nel = s->logical_bytes / 4;
-    hipLaunchKernelGGL(k_absmax, dim3(grid_for(nel)), dim3(kBlock), 0, st, (const uint32_t *)s->table, nel,
+    hipLaunchKernelGGL(k_absmax, dim3(grid_for_keys(nel)), dim3(kBlock), 0, st, (const uint32_t *)s->table, nel,
                        s->kind == PSK_KIND_CMS ? 1 : 0, s->ctr);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
@@ -529,12 +532,21 @@ template <class Src, class Op>
 static int launch_apply(const Src &src, const Op &op, uint64_t n, hipStream_t st, Mailbox *mb = nullptr)
 {
     if (n == 0) return PSK_OK;
-    const uint32_t grid = grid_for(n);
+    const uint32_t grid = grid_for_keys(n);
     if (mb && grid != 1) mailbox_disarm(mb);  // (the kernel's one workgroup posts it: see mailbox_post, psk_device.hpp)
     // (thread t of workgroup 0 takes keys t, t + kBlock ...: a batch of up to 64 keys needs one wave)
     hipLaunchKernelGGL((k_apply<Src, Op>), dim3(grid), dim3(n <= 64 ? 64 : kBlock), 0, st, src, op, n, mb ? mb->dev() : nullptr, mb ? mb->seq : 0u);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
+}
+
+// Dispatch a functor over the table's modulus as a compile-time constant: f(std::true_type{}) for a power-of-two table (mask), else
+// f(std::false_type{}) (Barrett).  Inside `[&](auto P) { ... }` the constant is P.value.
+template <class F>
+static inline int with_pow2(const psk_sketch *s, F &&f)
+{
+    if (s->pow2) return f(std::true_type{});
+    return f(std::false_type{});
 }
 
 static int check_hashes_width(const psk_sketch *s, int layout, uint32_t key_len)
@@ -603,6 +615,22 @@ static int finish(int where, const OutBuf *o, hipStream_t st, const Mailbox *mb 
         if (copy && o->is_pinned) memcpy(o->host, o->dev, o->bytes);
     }
     return PSK_OK;
+}
+
+// The tail of a direct (small-batch) call, when the partitioned path did not take the staged batch `b`: arm the mailbox (out_pinned: what the
+// kernel writes for the host lies in pinned memory -- true for updates, which return nothing, OutBuf::is_pinned for lookups), send ONE fixed-layout
+// key inside the kernel arguments (`data` is the caller's pointer, not the staged copy), launch k_apply with the op make_op(P) builds for the
+// table's modulus, and end the call (finish: mailbox or stream wait, results to the host; o = nullptr: no results).
+template <class MakeOp>
+static int direct_apply(psk_sketch *s, const Batch &b, const void *data, int where, bool out_pinned, const OutBuf *o, hipStream_t st, MakeOp &&make_op)
+{
+    Mailbox mb;  // (an update returns nothing, but a PSK_HOST call ends when the kernel has read the caller's keys: the same mailbox says so)
+    PSK_TRY(mailbox_arm(s, where, b.n, out_pinned, &mb));
+    KeysInline64 ik;
+    PSK_TRY(with_source_one(b, inline_key(b.layout, data, b.n, b.key_len, mb, &ik), [&](auto src) {
+        return with_pow2(s, [&](auto P) { return launch_apply(src, make_op(P), b.n, st, &mb); });
+    }));
+    return finish(where, o, st, &mb);
 }
 
 // ------------------------------------------------- partitioned (large-batch) path: options
@@ -784,14 +812,7 @@ extern "C" int psk_bloom_add(psk_sketch *s, int layout, const void *data, const 
     if (!s->pend.active) PSK_TRY(bloom_add_partitioned(s, b, st, &done));  // (a pending split lookup owns the bucket buffer)
     if (done) return finish(where, nullptr, st);
     PSK_TRY(clear_materialize(s, st));  // (the partitioned insert consumes a deferred clear; the direct kernel ORs into the table)
-    Mailbox mb;  // (an update returns nothing, but a PSK_HOST call ends when the kernel has read the caller's keys: the same mailbox says so)
-    PSK_TRY(mailbox_arm(s, where, n, true, &mb));
-    KeysInline64 ik;
-    PSK_TRY(with_source_one(b, inline_key(layout, data, n, key_len, mb, &ik), [&](auto src) {
-        if (s->pow2) return launch_apply(src, BloomAdd<true>{(uint32_t *)s->table, s->md, s->k}, n, st, &mb);
-        return launch_apply(src, BloomAdd<false>{(uint32_t *)s->table, s->md, s->k}, n, st, &mb);
-    }));
-    return finish(where, nullptr, st, &mb);
+    return direct_apply(s, b, data, where, true, nullptr, st, [&](auto P) { return BloomAdd<P.value>{(uint32_t *)s->table, s->md, s->k}; });
 }
 
 extern "C" int psk_bloom_check(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n,
@@ -811,14 +832,8 @@ extern "C" int psk_bloom_check(psk_sketch *s, int layout, const void *data, cons
         if (!s->pend.active) PSK_TRY(bloom_check_partitioned(s, b, (uint8_t *)o.dev, st, &done));
         if (done) return finish(where, &o, st);
     }
-    Mailbox mb;
-    PSK_TRY(mailbox_arm(s, where, n, o.is_pinned, &mb));
-    KeysInline64 ik;
-    PSK_TRY(with_source_one(b, inline_key(layout, data, n, key_len, mb, &ik), [&](auto src) {
-        if (s->pow2) return launch_apply(src, BloomCheck<true>{(const uint32_t *)s->table, s->md, s->k, (uint8_t *)o.dev}, n, st, &mb);
-        return launch_apply(src, BloomCheck<false>{(const uint32_t *)s->table, s->md, s->k, (uint8_t *)o.dev}, n, st, &mb);
-    }));
-    return finish(where, &o, st, &mb);
+    return direct_apply(s, b, data, where, o.is_pinned, &o, st,
+                        [&](auto P) { return BloomCheck<P.value>{(const uint32_t *)s->table, s->md, s->k, (uint8_t *)o.dev}; });
 }
 
 extern "C" int psk_bloom_indices(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n,
@@ -832,8 +847,7 @@ extern "C" int psk_bloom_indices(psk_sketch *s, int layout, const void *data, co
     Batch b;
     PSK_TRY(stage_batch(s->s_keys, s->s_offs, layout, data, offsets, n, key_len, where, st, &b));
     PSK_TRY(with_source(b, [&](auto src) {
-        if (s->pow2) return launch_apply(src, BloomIndexOut<true>{out_idx_dev, s->md, s->k}, n, st);
-        return launch_apply(src, BloomIndexOut<false>{out_idx_dev, s->md, s->k}, n, st);
+        return with_pow2(s, [&](auto P) { return launch_apply(src, BloomIndexOut<P.value>{out_idx_dev, s->md, s->k}, n, st); });
     }));
     return finish(where, nullptr, st);
 }
@@ -869,26 +883,20 @@ extern "C" int psk_bloom_check_finish(psk_sketch *s, uint8_t *out_dev, void *str
     PSK_TRY(bloom_check_finish_partitioned(s, out_dev, st, &redo));
     if (!s->pend.scattered) {  // batch / table not eligible for the partitioned path: plain direct lookup now
         return with_source(b, [&](auto src) {
-            if (s->pow2) return launch_apply(src, BloomCheck<true>{(const uint32_t *)s->table, s->md, s->k, out_dev}, b.n, st);
-            return launch_apply(src, BloomCheck<false>{(const uint32_t *)s->table, s->md, s->k, out_dev}, b.n, st);
+            return with_pow2(s, [&](auto P) { return launch_apply(src, BloomCheck<P.value>{(const uint32_t *)s->table, s->md, s->k, out_dev}, b.n, st); });
         });
     }
     if (redo) {  // exact redo of the first round, taken on the device only if a segment overflowed during begin
         const uint64_t cnt0 = b.n < s->pend.round_keys ? b.n : s->pend.round_keys;
         const uint32_t *flag = (const uint32_t *)s->s_flag.p;
         PSK_TRY(with_source(sub_batch(b, 0, cnt0), [&](auto src) {
-            using Src = decltype(src);
-            if (s->pow2) {
-                using Op = BloomCheck<true>;
-                hipLaunchKernelGGL((k_apply_if<Src, Op>), dim3(grid_for(cnt0)), dim3(kBlock), 0, st, flag, src,
+            return with_pow2(s, [&](auto P) {
+                using Op = BloomCheck<P.value>;
+                hipLaunchKernelGGL((k_apply_if<decltype(src), Op>), dim3(grid_for_keys(cnt0)), dim3(kBlock), 0, st, flag, src,
                                    Op{(const uint32_t *)s->table, s->md, s->k, out_dev}, cnt0);
-            } else {
-                using Op = BloomCheck<false>;
-                hipLaunchKernelGGL((k_apply_if<Src, Op>), dim3(grid_for(cnt0)), dim3(kBlock), 0, st, flag, src,
-                                   Op{(const uint32_t *)s->table, s->md, s->k, out_dev}, cnt0);
-            }
-            HIP_TRY(hipGetLastError());
-            return (int)PSK_OK;
+                HIP_TRY(hipGetLastError());
+                return (int)PSK_OK;
+            });
         }));
     }
     return PSK_OK;
@@ -952,15 +960,12 @@ extern "C" int psk_bloom_check_bits(psk_sketch *s, int layout, const void *data,
     }
     if (n && !packed) {
         PSK_TRY(with_source(b, [&](auto src) {
-            using Src = decltype(src);
-            if (s->pow2)
-                hipLaunchKernelGGL((k_bloom_check_bits<Src, true>), dim3(grid_for(n)), dim3(kBlock), 0, st, src,
+            return with_pow2(s, [&](auto P) {
+                hipLaunchKernelGGL((k_bloom_check_bits<decltype(src), P.value>), dim3(grid_for_keys(n)), dim3(kBlock), 0, st, src,
                                    (const uint32_t *)s->table, s->md, s->k, n, (unsigned long long *)o.dev, hits_dev);
-            else
-                hipLaunchKernelGGL((k_bloom_check_bits<Src, false>), dim3(grid_for(n)), dim3(kBlock), 0, st, src,
-                                   (const uint32_t *)s->table, s->md, s->k, n, (unsigned long long *)o.dev, hits_dev);
-            HIP_TRY(hipGetLastError());
-            return (int)PSK_OK;
+                HIP_TRY(hipGetLastError());
+                return (int)PSK_OK;
+            });
         }));
     }
     if (where == PSK_HOST) HIP_TRY(hipMemcpyAsync(hits, hits_dev, 8, hipMemcpyDeviceToHost, st));
@@ -975,7 +980,7 @@ static int account_weights(psk_sketch *s, const W *w_dev, uint64_t n, int which,
     if (n == 0) return PSK_OK;
     if (w_dev) {
         HIP_TRY(hipMemsetAsync(s->ctr + 6, 0, sizeof(long long), st));  // per-batch sum|w| (partitioned path wrap check)
-        hipLaunchKernelGGL((k_weight_sum<W>), dim3(grid_for(n) > 256 ? 256 : grid_for(n)), dim3(kBlock), 0, st, w_dev, n,
+        hipLaunchKernelGGL((k_weight_sum<W>), dim3(grid_for_keys(n) > 256 ? 256 : grid_for_keys(n)), dim3(kBlock), 0, st, w_dev, n,
                            s->ctr, which, bound_mult, (int)grow_bound);
     } else {
         hipLaunchKernelGGL(k_ctr_add, dim3(1), dim3(1), 0, st, s->ctr, which, (long long)n, grow_bound ? (long long)n * bound_mult : 0LL);
@@ -1011,24 +1016,28 @@ static int settle_acct(psk_sketch *s, const W *w_dev, uint64_t n, hipStream_t st
 // ----------------------------------------------------- CountingBloomFilter
 int64_t g_combine_keys = 1 << 26;  // keys per write-combining list (psk_set_option "combine_keys"): 1 GiB of 16-byte keys per list
 
+// the direct kernels of an unordered CBF update (w = nullptr: unit weights)
+static int cbf_apply_direct(psk_sketch *s, const Batch &b, const uint32_t *w, bool remove, hipStream_t st)
+{
+    unsigned long long *sat = (unsigned long long *)(s->ctr + PSK_CTR_SATURATED);
+    return with_source(b, [&](auto src) {
+        return with_pow2(s, [&](auto P) {
+            if (remove) return launch_apply(src, CbfSub<P.value>{(uint32_t *)s->table, s->md, s->k, w, sat - 1}, b.n, st);
+            return launch_apply(src, CbfAdd<P.value>{(uint32_t *)s->table, s->md, s->k, w, s->ctr, sat, false}, b.n, st);
+        });
+    });
+}
+
 // one unordered CBF update over a DEVICE-resident batch: add (countingbloom.py:135-155) or the unchecked decrement
 static int cbf_apply_device(psk_sketch *s, const Batch &b, const uint32_t *w, bool remove, hipStream_t st)
 {
     if (b.n == 0) return PSK_OK;
     PSK_TRY(post_acct(s, w, b.n, remove ? PSK_CTR_REMOVED : PSK_CTR_ADDED, (long long)s->k, st, !remove, false));
-    unsigned long long *sat = (unsigned long long *)(s->ctr + PSK_CTR_SATURATED);
     bool done = false;
     PSK_TRY(remove ? cbf_remove_partitioned(s, b, w, st, &done, 0, nullptr) : cbf_add_partitioned(s, b, w, st, &done));
     PSK_TRY(settle_acct(s, w, b.n, st));
     if (done) return PSK_OK;
-    return with_source(b, [&](auto src) {
-        if (remove) {
-            if (s->pow2) return launch_apply(src, CbfSub<true>{(uint32_t *)s->table, s->md, s->k, w, sat - 1}, b.n, st);
-            return launch_apply(src, CbfSub<false>{(uint32_t *)s->table, s->md, s->k, w, sat - 1}, b.n, st);
-        }
-        if (s->pow2) return launch_apply(src, CbfAdd<true>{(uint32_t *)s->table, s->md, s->k, w, s->ctr, sat, false}, b.n, st);
-        return launch_apply(src, CbfAdd<false>{(uint32_t *)s->table, s->md, s->k, w, s->ctr, sat, false}, b.n, st);
-    });
+    return cbf_apply_direct(s, b, w, remove, st);
 }
 
 // ---- write-combined updates as scattered probes (psk_sketch::scat, psk_nibble.hpp)
@@ -1055,57 +1064,52 @@ static int comb_appended(psk_sketch *s, hipStream_t st)
     return PSK_OK;
 }
 
-static int scat_zero(psk_sketch *s, bool add, bool rem, hipStream_t st)
+// does one of the mechanisms older than the update window hold updates: key lists, borrowed lists, the scattered list
+static bool older_updates_pending(const psk_sketch *s)
+{
+    return s->comb.add.n || s->comb.rem.n || s->comb.badd.n() || s->comb.brem.n() || (s->scat.ready && s->scat.add.n);
+}
+
+static int scat_zero(psk_sketch *s, hipStream_t st)
 {
     const uint64_t nseg = (uint64_t)s->scat.g.nbuckets * s->scat.g.nwg;
-    uint32_t *a = add ? (uint32_t *)s->scat.add.cnt.p : nullptr, *b = rem ? (uint32_t *)s->scat.rem.cnt.p : nullptr;
-    if (!a && !b) return PSK_OK;
-    hipLaunchKernelGGL(k_zero_u32, dim3(256), dim3(256), 0, st, a ? a : b, nseg, (a && b) ? b : nullptr, (a && b) ? nseg : 0ULL);
+    if (!s->scat.add.cnt.p) return PSK_OK;
+    hipLaunchKernelGGL(k_zero_u32, dim3(256), dim3(256), 0, st, (uint32_t *)s->scat.add.cnt.p, nseg);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
 }
 
 static int scat_drop(psk_sketch *s, hipStream_t st)
 {
-    if (!s->scat.ready || (s->scat.add.n == 0 && s->scat.rem.n == 0)) return PSK_OK;
+    if (!s->scat.ready || s->scat.add.n == 0) return PSK_OK;
     PSK_TRY(comb_order(s, st));
-    PSK_TRY(scat_zero(s, s->scat.add.n != 0, s->scat.rem.n != 0, st));
-    s->scat.add.n = s->scat.rem.n = 0;
+    PSK_TRY(scat_zero(s, st));
+    s->scat.add.n = 0;
     return PSK_OK;
 }
 
-// apply the scattered lists: adds, then decrements (a remove whose add waits in the same window must find it applied).
-// Enough probes: one pass over the table (k_nib_apply; both lists in ONE launch when both are due); few: a drain with atomics.
+// apply the scattered list.  Enough probes: one pass over the table (k_nib_apply); few: a drain with atomics.
 static int scat_flush(psk_sketch *s, hipStream_t st)
 {
-    if (!s->scat.ready || (s->scat.add.n == 0 && s->scat.rem.n == 0)) return PSK_OK;
+    if (!s->scat.ready || s->scat.add.n == 0) return PSK_OK;
     PSK_TRY(comb_order(s, st));
-    const uint64_t na = s->scat.add.n, nr = s->scat.rem.n;
-    s->scat.add.n = s->scat.rem.n = 0;  // (cleared first: a failure must not re-apply the lists on the next call)
+    const uint64_t na = s->scat.add.n;
+    s->scat.add.n = 0;  // (cleared first: a failure must not re-apply the list on the next call)
     PartGeom g = s->scat.g;
     const uint64_t per_seg = (uint64_t)g.nbuckets * g.nwg * 6;
-    g.dense = ((na > nr ? na : nr) * s->k / per_seg) < (uint64_t)g_part_dense_groups ? 1u : 0u;
+    g.dense = (na * s->k / per_seg) < (uint64_t)g_part_dense_groups ? 1u : 0u;
     const size_t lds = (size_t)1 << (g.shift - 1);
     unsigned long long *sat = (unsigned long long *)(s->ctr + PSK_CTR_SATURATED);
-    const bool pass_a = na * s->k >= s->m / 8, pass_r = nr * s->k >= s->m / 8;
-    auto launch = [&](auto kern, const psk_sketch::ScatList *la, const psk_sketch::ScatList *lb, uint32_t direct) {
-        PSK_TRY(set_dyn_lds(kern, lds));
-        hipLaunchKernelGGL(kern, dim3(g.nbuckets), dim3(kApplyThreads), lds, st, (uint32_t *)s->table, s->m, g, (const uint32_t *)la->cnt.p, (const uint4 *)la->part.p,
-                           (const uint32_t *)(lb ? lb->cnt.p : nullptr), (const uint4 *)(lb ? lb->part.p : nullptr), sat, direct, g);
-        HIP_TRY(hipGetLastError());
-        return (int)PSK_OK;
-    };
-    if (na && nr && pass_a && pass_r) {
-        PSK_TRY(launch(k_nib_apply<2>, &s->scat.add, &s->scat.rem, 0u));
-    } else {
-        if (na) PSK_TRY(launch(k_nib_apply<0>, &s->scat.add, nullptr, pass_a ? 0u : 1u));
-        if (nr) PSK_TRY(launch(k_nib_apply<1>, &s->scat.rem, nullptr, pass_r ? 0u : 1u));
-    }
-    return scat_zero(s, na != 0, nr != 0, st);
+    const uint32_t direct = na * s->k >= s->m / 8 ? 0u : 1u;
+    PSK_TRY(set_dyn_lds(k_nib_apply<0>, lds));
+    hipLaunchKernelGGL(k_nib_apply<0>, dim3(g.nbuckets), dim3(kApplyThreads), lds, st, (uint32_t *)s->table, s->m, g, (const uint32_t *)s->scat.add.cnt.p,
+                       (const uint4 *)s->scat.add.part.p, sat, direct);
+    HIP_TRY(hipGetLastError());
+    return scat_zero(s, st);
 }
 
-// Hand a unit-weight batch over as scattered probes.  cap: keys per list; *done = false: not eligible (nothing was launched / changed).
-static int scat_append(psk_sketch *s, const Batch &b, bool neg, uint64_t cap, hipStream_t st, bool *done)
+// Hand a unit-weight batch of adds over as scattered probes.  cap: keys the list holds; *done = false: not eligible (nothing was launched / changed).
+static int scat_append(psk_sketch *s, const Batch &b, uint64_t cap, hipStream_t st, bool *done)
 {
     *done = false;
     {   // a list must stay within what one fold's 4-bit deltas hold (nib_load_ok): ~2.5 probes per counter
@@ -1122,11 +1126,10 @@ static int scat_append(psk_sketch *s, const Batch &b, bool neg, uint64_t cap, hi
         s->scat.cap = cap;
         s->scat.ready = true;
     }
-    psk_sketch::ScatList &l = neg ? s->scat.rem : s->scat.add;
+    psk_sketch::ScatList &l = s->scat.add;
     if (l.n + b.n > cap) PSK_TRY(flush_combined(s, st));
     const PartGeom &g = s->scat.g;
     const uint64_t part_bytes = (uint64_t)g.nbuckets * g.nwg * g.segcap * 16 + 256, cnt_bytes = (uint64_t)g.nbuckets * g.nwg * 4 + 128;
-    if (neg) return PSK_OK;  // (decrements stay out of the persistent segments: an overflowing segment would apply them ahead of the window's adds)
     if (l.part.cap < part_bytes || l.cnt.cap < cnt_bytes) {  // first use (or released): allocate, counts start at zero
         if (g_scratch_budget > 0 && (int64_t)(part_bytes + cnt_bytes) > g_scratch_budget) return PSK_OK;  // (not taken: the direct path serves)
         if (ensure(l.part, part_bytes) != PSK_OK || ensure(l.cnt, cnt_bytes) != PSK_OK) return PSK_OK;    // out of memory costs the shortcut, not the add
@@ -1135,7 +1138,7 @@ static int scat_append(psk_sketch *s, const Batch &b, bool neg, uint64_t cap, hi
     }
     PSK_TRY(comb_order(s, st));  // (appends are ordered among themselves too: two streams must not race on the cursors)
     bool appended = false;
-    PSK_TRY(cbf_scat_append(s, b, neg ? 1 : 0, st, &appended));
+    PSK_TRY(cbf_scat_append(s, b, st, &appended));
     if (!appended) return PSK_OK;  // layout without a partitioned instantiation
     l.n += b.n;
     PSK_TRY(comb_appended(s, st));
@@ -1165,16 +1168,8 @@ static int borrowed_flush(psk_sketch *s, psk_sketch::BorrowList &bl, bool remove
     PSK_TRY(cbf_unit_multi_partitioned(s, (const void *const *)base_dev, start_dev, nb, n, remove ? 1 : 0, st, &done));
     if (done) return PSK_OK;
     for (uint32_t j = 0; j < nb; ++j) {  // table not eligible after all (option changed meanwhile): batch by batch through the general path
-        Batch b{PSK_KEYS_FIXED, bases[j], nullptr, starts[j + 1] - starts[j], 16};
-        unsigned long long *sat = (unsigned long long *)(s->ctr + PSK_CTR_SATURATED);
-        PSK_TRY(with_source(b, [&](auto src) {
-            if (remove) {
-                if (s->pow2) return launch_apply(src, CbfSub<true>{(uint32_t *)s->table, s->md, s->k, nullptr, sat - 1}, b.n, st);
-                return launch_apply(src, CbfSub<false>{(uint32_t *)s->table, s->md, s->k, nullptr, sat - 1}, b.n, st);
-            }
-            if (s->pow2) return launch_apply(src, CbfAdd<true>{(uint32_t *)s->table, s->md, s->k, nullptr, s->ctr, sat, false}, b.n, st);
-            return launch_apply(src, CbfAdd<false>{(uint32_t *)s->table, s->md, s->k, nullptr, s->ctr, sat, false}, b.n, st);
-        }));
+        const Batch b{PSK_KEYS_FIXED, bases[j], nullptr, starts[j + 1] - starts[j], 16};
+        PSK_TRY(cbf_apply_direct(s, b, nullptr, remove, st));
     }
     return PSK_OK;
 }
@@ -1354,7 +1349,7 @@ int flush_combined(psk_sketch *s, hipStream_t st)
     if (s->kind != PSK_KIND_CBF) return PSK_OK;
     if (s->win.n) {  // (the window holds what arrived AFTER anything the older mechanisms below hold: see win_append's callers)
         ++s->table_version;
-        if (s->comb.add.n || s->comb.rem.n || s->comb.badd.n() || s->comb.brem.n() || (s->scat.ready && (s->scat.add.n || s->scat.rem.n))) {
+        if (older_updates_pending(s)) {
             std::vector<psk_sketch::WinBatch> keep;
             keep.swap(s->win.batches);
             const uint64_t wn = s->win.n, wc = s->win.copied;
@@ -1366,13 +1361,11 @@ int flush_combined(psk_sketch *s, hipStream_t st)
         }
         PSK_TRY(win_flush(s, st));
     }
-    const bool keys_pending = s->comb.add.n != 0 || s->comb.rem.n != 0 || s->comb.badd.n() != 0 || s->comb.brem.n() != 0;
-    const bool scat_pending = s->scat.ready && (s->scat.add.n != 0 || s->scat.rem.n != 0);
-    if (!keys_pending && !scat_pending) return PSK_OK;
+    if (!older_updates_pending(s)) return PSK_OK;
     ++s->table_version;  // (also from the read-only entry points: what waited reaches the table now)
     PSK_TRY(comb_order(s, st));
     // adds first: a remove whose add waits in the same window must find it applied.  Two mechanisms may hold updates -- key lists
-    // (weighted batches, tables below the nibble geometry) and scattered probes: all adds of both, then all removes of both.
+    // (weighted batches, tables below the nibble geometry; adds and removes) and scattered probes (adds only): all adds of both, then the removes.
     auto key_list = [&](int pass) {
         psk_sketch::PendList &l = pass == 0 ? s->comb.add : s->comb.rem;
         if (l.n == 0) return (int)PSK_OK;
@@ -1384,12 +1377,7 @@ int flush_combined(psk_sketch *s, hipStream_t st)
     };
     PSK_TRY(key_list(0));
     PSK_TRY(borrowed_flush(s, s->comb.badd, false, st));
-    if (scat_pending && (s->comb.rem.n != 0 || s->comb.brem.n() != 0) && s->scat.add.n != 0) {  // key-list removes wait: the scattered adds must land before them
-        const uint64_t nr = s->scat.rem.n;
-        s->scat.rem.n = 0;
-        PSK_TRY(scat_flush(s, st));
-        s->scat.rem.n = nr;
-    }
+    if (s->comb.rem.n != 0 || s->comb.brem.n() != 0) PSK_TRY(scat_flush(s, st));  // key-list removes wait: the scattered adds must land before them
     PSK_TRY(key_list(1));
     PSK_TRY(borrowed_flush(s, s->comb.brem, true, st));
     return scat_flush(s, st);
@@ -1474,7 +1462,7 @@ extern "C" int psk_cbf_add(psk_sketch *s, int layout, const void *data, const ui
     if (where != PSK_HOST && where != PSK_DEVICE && where != PSK_DEVICE_BORROWED) return fail(PSK_EINVAL, "`where` must be PSK_HOST, PSK_DEVICE or PSK_DEVICE_BORROWED");
     if (win_eligible(s, layout, data, key_len, weights, n)) {
         // (what the older write-combining mechanisms hold arrived earlier: it goes first)
-        if (s->comb.add.n || s->comb.rem.n || s->comb.badd.n() || s->comb.brem.n() || (s->scat.ready && (s->scat.add.n || s->scat.rem.n))) PSK_TRY(flush_combined(s, st));
+        if (older_updates_pending(s)) PSK_TRY(flush_combined(s, st));
         bool taken = false;
         PSK_TRY(win_append(s, data, n, false, where == PSK_DEVICE_BORROWED && ((uintptr_t)data & 15) ? PSK_DEVICE : where, st, &taken));
         if (taken) return PSK_OK;  // (else: no memory for the window's key list -- the batch goes on below like any other)
@@ -1488,10 +1476,10 @@ extern "C" int psk_cbf_add(psk_sketch *s, int layout, const void *data, const ui
     // (16-byte keys wait in the update window above; the other layouts here.  An append launches min(256, tiles) workgroups and workgroup i
     // always fills segment column i: batches of fewer than 256 tiles would pile the whole list into a few columns, which overflow long before
     // the list is full -- such batches take the direct kernel, as before round 3.)
-    if (!weights && g_auto_combine != 0 && s->win.n == 0 && s->comb.rem.n == 0 && s->comb.brem.n() == 0 && s->scat.rem.n == 0 && (int64_t)n >= g_part_min_keys &&
+    if (!weights && g_auto_combine != 0 && s->win.n == 0 && s->comb.rem.n == 0 && s->comb.brem.n() == 0 && (int64_t)n >= g_part_min_keys &&
         n >= (256u * 2048u * 7u) / (s->k ? s->k : 1u) && n * (uint64_t)s->k < s->m / 8 && g_auto_combine_keys > 0) {
         bool taken = false;
-        PSK_TRY(scat_append(s, b, false, (uint64_t)g_auto_combine_keys, st, &taken));
+        PSK_TRY(scat_append(s, b, (uint64_t)g_auto_combine_keys, st, &taken));
         if (taken) {
             PSK_TRY(account_weights(s, (const uint32_t *)nullptr, n, PSK_CTR_ADDED, (long long)s->k, st, true));
             return finish(where, nullptr, st);
@@ -1508,14 +1496,7 @@ extern "C" int psk_cbf_add(psk_sketch *s, int layout, const void *data, const ui
         PSK_TRY(settle_acct(s, w, n, st));
         if (done) return finish(where, nullptr, st);
     }
-    Mailbox mb;
-    PSK_TRY(mailbox_arm(s, where, n, true, &mb));
-    KeysInline64 ik;
-    PSK_TRY(with_source_one(b, inline_key(layout, data, n, key_len, mb, &ik), [&](auto src) {
-        if (s->pow2) return launch_apply(src, CbfAdd<true>{(uint32_t *)s->table, s->md, s->k, w, s->ctr, sat, false}, n, st, &mb);
-        return launch_apply(src, CbfAdd<false>{(uint32_t *)s->table, s->md, s->k, w, s->ctr, sat, false}, n, st, &mb);
-    }));
-    return finish(where, nullptr, st, &mb);
+    return direct_apply(s, b, data, where, true, nullptr, st, [&](auto P) { return CbfAdd<P.value>{(uint32_t *)s->table, s->md, s->k, w, s->ctr, sat, false}; });
 }
 
 // countingbloom.py:198-203 for a whole batch: from the min over the key's counters (a lookup) to the amount actually removed
@@ -1590,18 +1571,17 @@ static int cbf_remove_exact(psk_sketch *s, const Batch &b, const uint32_t *w, hi
     if (big) PSK_TRY(cbf_check_partitioned(s, b, s->k, mins, st, &looked));
     if (!looked) {
         PSK_TRY(with_source(b, [&](auto src) {
-            if (s->pow2) return launch_apply(src, CbfCheck<true>{(const uint32_t *)s->table, s->md, s->k, mins}, b.n, st);
-            return launch_apply(src, CbfCheck<false>{(const uint32_t *)s->table, s->md, s->k, mins}, b.n, st);
+            return with_pow2(s, [&](auto P) { return launch_apply(src, CbfCheck<P.value>{(const uint32_t *)s->table, s->md, s->k, mins}, b.n, st); });
         }));
     }
     PSK_TRY(ensure(s->s_flag, 8));
     uint32_t *flag = (uint32_t *)s->s_flag.p;
     HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
-    hipLaunchKernelGGL(k_cbf_to_remove, dim3(grid_for(b.n) > 1024 ? 1024 : grid_for(b.n)), dim3(kBlock), 0, st, (const uint32_t *)mins, w, b.n, amount, flag);
+    hipLaunchKernelGGL(k_cbf_to_remove, dim3(grid_for_keys(b.n) > 1024 ? 1024 : grid_for_keys(b.n)), dim3(kBlock), 0, st, (const uint32_t *)mins, w, b.n, amount, flag);
     HIP_TRY(hipGetLastError());
     // the amounts' sum: into a scratch block (booked once the verdict is in), and as this round's sum |w| for pass 2's wrap check
     HIP_TRY(hipMemsetAsync(tmp, 0, sizeof(long long) * PSK_CTR_COUNT, st));
-    hipLaunchKernelGGL((k_weight_sum<uint32_t>), dim3(grid_for(b.n) > 256 ? 256 : grid_for(b.n)), dim3(kBlock), 0, st, (const uint32_t *)amount, b.n, tmp,
+    hipLaunchKernelGGL((k_weight_sum<uint32_t>), dim3(grid_for_keys(b.n) > 256 ? 256 : grid_for_keys(b.n)), dim3(kBlock), 0, st, (const uint32_t *)amount, b.n, tmp,
                        (int)PSK_CTR_REMOVED, (long long)s->k, 0);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(s->ctr + 6, tmp + 6, sizeof(long long), hipMemcpyDeviceToDevice, st));
@@ -1616,8 +1596,7 @@ static int cbf_remove_exact(psk_sketch *s, const Batch &b, const uint32_t *w, hi
         }
         if (*partitioned) return (int)PSK_OK;
         return with_source(b, [&](auto src) {
-            if (s->pow2) return launch_apply(src, CbfSubChecked<true>{(uint32_t *)s->table, s->md, s->k, amount, flag, opt == 2}, b.n, st);
-            return launch_apply(src, CbfSubChecked<false>{(uint32_t *)s->table, s->md, s->k, amount, flag, opt == 2}, b.n, st);
+            return with_pow2(s, [&](auto P) { return launch_apply(src, CbfSubChecked<P.value>{(uint32_t *)s->table, s->md, s->k, amount, flag, opt == 2}, b.n, st); });
         });
     };
     bool part1 = false, part2 = false;
@@ -1636,7 +1615,7 @@ static int cbf_remove_exact(psk_sketch *s, const Batch &b, const uint32_t *w, hi
     const int64_t *w64 = nullptr;
     if (w) {
         int64_t *dst = (int64_t *)(tmp + PSK_CTR_COUNT + 2);
-        hipLaunchKernelGGL(k_widen_u32, dim3(grid_for(b.n) > 1024 ? 1024 : grid_for(b.n)), dim3(kBlock), 0, st, w, b.n, dst);
+        hipLaunchKernelGGL(k_widen_u32, dim3(grid_for_keys(b.n) > 1024 ? 1024 : grid_for_keys(b.n)), dim3(kBlock), 0, st, w, b.n, dst);
         HIP_TRY(hipGetLastError());
         w64 = dst;
     }
@@ -1646,15 +1625,12 @@ static int cbf_remove_exact(psk_sketch *s, const Batch &b, const uint32_t *w, hi
         wide = (uint64_t *)s->s_out.p;
     }
     return with_source(b, [&](auto src) {
-        using Src = decltype(src);
-        if (s->pow2)
-            hipLaunchKernelGGL((k_cbf_ordered<Src, true>), dim3(1), dim3(64), 0, st, src, (uint32_t *)s->table, s->md, s->k, w64, (int)PSK_OP_REMOVE, b.n,
+        return with_pow2(s, [&](auto P) {
+            hipLaunchKernelGGL((k_cbf_ordered<decltype(src), P.value>), dim3(1), dim3(64), 0, st, src, (uint32_t *)s->table, s->md, s->k, w64, (int)PSK_OP_REMOVE, b.n,
                                (uint32_t *)nullptr, (unsigned long long *)s->ctr, wide, (uint32_t *)nullptr, 0u);
-        else
-            hipLaunchKernelGGL((k_cbf_ordered<Src, false>), dim3(1), dim3(64), 0, st, src, (uint32_t *)s->table, s->md, s->k, w64, (int)PSK_OP_REMOVE, b.n,
-                               (uint32_t *)nullptr, (unsigned long long *)s->ctr, wide, (uint32_t *)nullptr, 0u);
-        HIP_TRY(hipGetLastError());
-        return (int)PSK_OK;
+            HIP_TRY(hipGetLastError());
+            return (int)PSK_OK;
+        });
     });
 }
 
@@ -1667,15 +1643,12 @@ static int cbf_remove_device(psk_sketch *s, const Batch &b, const uint32_t *w, h
     // (option "remove_exact" = 0, bench A/B: the one-kernel form -- per key: read the k counters, decide, subtract; exact for
     // well-formed batches, deviations tallied in PSK_CTR_VIOLATIONS)
     return with_source(b, [&](auto src) {
-        using Src = decltype(src);
-        if (s->pow2)
-            hipLaunchKernelGGL((k_cbf_remove<Src, true>), dim3(grid_for(b.n)), dim3(kBlock), 0, st, src, (uint32_t *)s->table, s->md, s->k, w, b.n,
+        return with_pow2(s, [&](auto P) {
+            hipLaunchKernelGGL((k_cbf_remove<decltype(src), P.value>), dim3(grid_for_keys(b.n)), dim3(kBlock), 0, st, src, (uint32_t *)s->table, s->md, s->k, w, b.n,
                                (unsigned long long *)s->ctr);
-        else
-            hipLaunchKernelGGL((k_cbf_remove<Src, false>), dim3(grid_for(b.n)), dim3(kBlock), 0, st, src, (uint32_t *)s->table, s->md, s->k, w, b.n,
-                               (unsigned long long *)s->ctr);
-        HIP_TRY(hipGetLastError());
-        return (int)PSK_OK;
+            HIP_TRY(hipGetLastError());
+            return (int)PSK_OK;
+        });
     });
 }
 
@@ -1689,7 +1662,7 @@ extern "C" int psk_cbf_remove(psk_sketch *s, int layout, const void *data, const
     if (win_eligible(s, layout, data, key_len, weights, n)) {
         // A small batch into a big table: it waits in the update window (with the adds around it, in order) for a shared pass over
         // the table; the flush proves that it would have removed every key at this point of the stream, or replays it right here.
-        if (s->comb.add.n || s->comb.rem.n || s->comb.badd.n() || s->comb.brem.n() || (s->scat.ready && (s->scat.add.n || s->scat.rem.n))) PSK_TRY(flush_combined(s, st));
+        if (older_updates_pending(s)) PSK_TRY(flush_combined(s, st));
         bool taken = false;
         PSK_TRY(win_append(s, data, n, true, where == PSK_DEVICE_BORROWED && ((uintptr_t)data & 15) ? PSK_DEVICE : where, st, &taken));
         if (taken) return PSK_OK;
@@ -1726,14 +1699,7 @@ extern "C" int psk_cbf_check(psk_sketch *s, int layout, const void *data, const 
         PSK_TRY(rc);
         if (done) return finish(where, &o, st);
     }
-    Mailbox mb;
-    PSK_TRY(mailbox_arm(s, where, n, o.is_pinned, &mb));
-    KeysInline64 ik;
-    PSK_TRY(with_source_one(b, inline_key(layout, data, n, key_len, mb, &ik), [&](auto src) {
-        if (s->pow2) return launch_apply(src, CbfCheck<true>{(const uint32_t *)s->table, s->md, kk, (uint32_t *)o.dev}, n, st, &mb);
-        return launch_apply(src, CbfCheck<false>{(const uint32_t *)s->table, s->md, kk, (uint32_t *)o.dev}, n, st, &mb);
-    }));
-    return finish(where, &o, st, &mb);
+    return direct_apply(s, b, data, where, o.is_pinned, &o, st, [&](auto P) { return CbfCheck<P.value>{(const uint32_t *)s->table, s->md, kk, (uint32_t *)o.dev}; });
 }
 
 extern "C" int psk_cbf_update_ordered(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n,
@@ -1762,15 +1728,12 @@ extern "C" int psk_cbf_update_ordered(psk_sketch *s, int layout, const void *dat
     KeysInline64 ik;
     if (n) {
         PSK_TRY(with_source_one(b, inline_key(layout, data, n, key_len, mb, &ik), [&](auto src) {
-            using Src = decltype(src);
-            if (s->pow2)
-                hipLaunchKernelGGL((k_cbf_ordered<Src, true>), dim3(1), dim3(64), 0, st, src, (uint32_t *)s->table, s->md,
+            return with_pow2(s, [&](auto P) {
+                hipLaunchKernelGGL((k_cbf_ordered<decltype(src), P.value>), dim3(1), dim3(64), 0, st, src, (uint32_t *)s->table, s->md,
                                    s->k, w, opmode, n, (uint32_t *)(out ? o.dev : nullptr), (unsigned long long *)s->ctr, wide, mb.dev(), mb.seq);
-            else
-                hipLaunchKernelGGL((k_cbf_ordered<Src, false>), dim3(1), dim3(64), 0, st, src, (uint32_t *)s->table, s->md,
-                                   s->k, w, opmode, n, (uint32_t *)(out ? o.dev : nullptr), (unsigned long long *)s->ctr, wide, mb.dev(), mb.seq);
-            HIP_TRY(hipGetLastError());
-            return (int)PSK_OK;
+                HIP_TRY(hipGetLastError());
+                return (int)PSK_OK;
+            });
         }));
     }
     return finish(where, &o, st, &mb);
@@ -1796,15 +1759,7 @@ static int cms_update(psk_sketch *s, int layout, const void *data, const uint64_
         PSK_TRY(settle_acct(s, w, n, st));
         if (done) return finish(where, nullptr, st);
     }
-    Mailbox mb;
-    PSK_TRY(mailbox_arm(s, where, n, true, &mb));
-    KeysInline64 ik;
-    PSK_TRY(with_source_one(b, inline_key(layout, data, n, key_len, mb, &ik), [&](auto src) {
-        if (s->pow2)
-            return launch_apply(src, CmsAdd<true, NEG>{(int32_t *)s->table, s->md, s->k, w, s->ctr, sat, false}, n, st, &mb);
-        return launch_apply(src, CmsAdd<false, NEG>{(int32_t *)s->table, s->md, s->k, w, s->ctr, sat, false}, n, st, &mb);
-    }));
-    return finish(where, nullptr, st, &mb);
+    return direct_apply(s, b, data, where, true, nullptr, st, [&](auto P) { return CmsAdd<P.value, NEG>{(int32_t *)s->table, s->md, s->k, w, s->ctr, sat, false}; });
 }
 
 extern "C" int psk_cms_add(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n,
@@ -1837,14 +1792,7 @@ extern "C" int psk_cms_check(psk_sketch *s, int layout, const void *data, const 
         PSK_TRY(cms_check_partitioned(s, b, query, 0, o.dev, st, &done));
         if (done) return finish(where, &o, st);
     }
-    Mailbox mb;
-    PSK_TRY(mailbox_arm(s, where, n, o.is_pinned, &mb));
-    KeysInline64 ik;
-    PSK_TRY(with_source_one(b, inline_key(layout, data, n, key_len, mb, &ik), [&](auto src) {
-        if (s->pow2) return launch_apply(src, CmsCheck<true>{(const int32_t *)s->table, s->md, s->k, (int32_t *)o.dev, mean}, n, st, &mb);
-        return launch_apply(src, CmsCheck<false>{(const int32_t *)s->table, s->md, s->k, (int32_t *)o.dev, mean}, n, st, &mb);
-    }));
-    return finish(where, &o, st, &mb);
+    return direct_apply(s, b, data, where, o.is_pinned, &o, st, [&](auto P) { return CmsCheck<P.value>{(const int32_t *)s->table, s->md, s->k, (int32_t *)o.dev, mean}; });
 }
 
 extern "C" int psk_cms_check_meanmin(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n,
@@ -1864,17 +1812,13 @@ extern "C" int psk_cms_check_meanmin(psk_sketch *s, int layout, const void *data
         PSK_TRY(ensure(s->s_aux, 8ULL * s->k));
         if (n) {
             PSK_TRY(with_source(b, [&](auto src) {
-                using Src = decltype(src);
-                if (s->pow2)
-                    hipLaunchKernelGGL((k_cms_ordered<Src, true>), dim3(1), dim3(64), 0, st, src, (int32_t *)s->table, s->md, s->k,
+                return with_pow2(s, [&](auto P) {
+                    hipLaunchKernelGGL((k_cms_ordered<decltype(src), P.value>), dim3(1), dim3(64), 0, st, src, (int32_t *)s->table, s->md, s->k,
                                        (const int64_t *)nullptr, 3, (int)PSK_Q_MEANMIN, elements_added, n, (int64_t *)o.dev, s->ctr, (int64_t *)s->s_aux.p,
                                        (uint32_t *)nullptr, 0u);
-                else
-                    hipLaunchKernelGGL((k_cms_ordered<Src, false>), dim3(1), dim3(64), 0, st, src, (int32_t *)s->table, s->md, s->k,
-                                       (const int64_t *)nullptr, 3, (int)PSK_Q_MEANMIN, elements_added, n, (int64_t *)o.dev, s->ctr, (int64_t *)s->s_aux.p,
-                                       (uint32_t *)nullptr, 0u);
-                HIP_TRY(hipGetLastError());
-                return (int)PSK_OK;
+                    HIP_TRY(hipGetLastError());
+                    return (int)PSK_OK;
+                });
             }));
         }
         return finish(where, &o, st);
@@ -1884,15 +1828,8 @@ extern "C" int psk_cms_check_meanmin(psk_sketch *s, int layout, const void *data
         PSK_TRY(cms_check_partitioned(s, b, PSK_Q_MEANMIN, elements_added, o.dev, st, &done));
         if (done) return finish(where, &o, st);
     }
-    Mailbox mb;
-    PSK_TRY(mailbox_arm(s, where, n, o.is_pinned, &mb));
-    KeysInline64 ik;
-    PSK_TRY(with_source_one(b, inline_key(layout, data, n, key_len, mb, &ik), [&](auto src) {
-        if (s->pow2)
-            return launch_apply(src, CmsCheckMeanMin<true>{(const int32_t *)s->table, s->md, s->k, elements_added, (int64_t *)o.dev}, n, st, &mb);
-        return launch_apply(src, CmsCheckMeanMin<false>{(const int32_t *)s->table, s->md, s->k, elements_added, (int64_t *)o.dev}, n, st, &mb);
-    }));
-    return finish(where, &o, st, &mb);
+    return direct_apply(s, b, data, where, o.is_pinned, &o, st,
+                        [&](auto P) { return CmsCheckMeanMin<P.value>{(const int32_t *)s->table, s->md, s->k, elements_added, (int64_t *)o.dev}; });
 }
 
 extern "C" int psk_cms_update_ordered(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n,
@@ -1921,15 +1858,12 @@ extern "C" int psk_cms_update_ordered(psk_sketch *s, int layout, const void *dat
     if (mb.word && n == 1 && weights && weights[0] == 1) w = nullptr;  // (a null weight list means 1: no read of the pinned page for `cms.add(key)`)
     KeysInline64 ik;
     PSK_TRY(with_source_one(b, inline_key(layout, data, n, key_len, mb, &ik), [&](auto src) {
-        using Src = decltype(src);
-        if (s->pow2)
-            hipLaunchKernelGGL((k_cms_ordered<Src, true>), dim3(1), dim3(64), 0, st, src, (int32_t *)s->table, s->md, s->k, w,
+        return with_pow2(s, [&](auto P) {
+            hipLaunchKernelGGL((k_cms_ordered<decltype(src), P.value>), dim3(1), dim3(64), 0, st, src, (int32_t *)s->table, s->md, s->k, w,
                                opmode, query, elements_added_in, n, (int64_t *)(out ? o.dev : nullptr), s->ctr, wide, mb.dev(), mb.seq);
-        else
-            hipLaunchKernelGGL((k_cms_ordered<Src, false>), dim3(1), dim3(64), 0, st, src, (int32_t *)s->table, s->md, s->k, w,
-                               opmode, query, elements_added_in, n, (int64_t *)(out ? o.dev : nullptr), s->ctr, wide, mb.dev(), mb.seq);
-        HIP_TRY(hipGetLastError());
-        return (int)PSK_OK;
+            HIP_TRY(hipGetLastError());
+            return (int)PSK_OK;
+        });
     }));
     return finish(where, &o, st, &mb);
 }
@@ -1951,7 +1885,7 @@ extern "C" int psk_fnv1a_hash(int layout, const void *data, const uint64_t *offs
     if (n && depth) {
         PSK_TRY(with_source(b, [&](auto src) {
             using Src = decltype(src);
-            hipLaunchKernelGGL((k_hash<Src>), dim3(grid_for(n)), dim3(kBlock), 0, st, src, (uint64_t *)o.dev, depth, n);
+            hipLaunchKernelGGL((k_hash<Src>), dim3(grid_for_keys(n)), dim3(kBlock), 0, st, src, (uint64_t *)o.dev, depth, n);
             HIP_TRY(hipGetLastError());
             return (int)PSK_OK;
         }));
@@ -1999,7 +1933,7 @@ extern "C" int psk_table_or(void *dst, const void *src, uint64_t nwords32, int d
     PSK_TRY(check_vec(dst, src, nwords32));
     PSK_USE_DEVICE(device);
     if (!nwords32) return PSK_OK;
-    hipLaunchKernelGGL((k_table_binop<OpOr>), dim3(grid_for(nwords32 / 4)), dim3(kBlock), 0, (hipStream_t)stream, (uint4 *)dst,
+    hipLaunchKernelGGL((k_table_binop<OpOr>), dim3(grid_for_keys(nwords32 / 4)), dim3(kBlock), 0, (hipStream_t)stream, (uint4 *)dst,
                        (const uint4 *)src, nwords32 / 4, OpOr{});
     HIP_TRY(hipGetLastError());
     return PSK_OK;
@@ -2010,7 +1944,7 @@ extern "C" int psk_table_and(void *dst, const void *src, uint64_t nwords32, int 
     PSK_TRY(check_vec(dst, src, nwords32));
     PSK_USE_DEVICE(device);
     if (!nwords32) return PSK_OK;
-    hipLaunchKernelGGL((k_table_binop<OpAnd>), dim3(grid_for(nwords32 / 4)), dim3(kBlock), 0, (hipStream_t)stream, (uint4 *)dst,
+    hipLaunchKernelGGL((k_table_binop<OpAnd>), dim3(grid_for_keys(nwords32 / 4)), dim3(kBlock), 0, (hipStream_t)stream, (uint4 *)dst,
                        (const uint4 *)src, nwords32 / 4, OpAnd{});
     HIP_TRY(hipGetLastError());
     return PSK_OK;
@@ -2026,7 +1960,7 @@ static int table_count(const void *tab, uint64_t nwords32, int mode, uint64_t *o
     HIP_TRY(hipMalloc((void **)&d, 8));
     hipError_t e = hipMemsetAsync(d, 0, 8, st);
     if (e == hipSuccess && nwords32) {
-        const int g = grid_for(nwords32 / 4) > 1024 ? 1024 : grid_for(nwords32 / 4);
+        const int g = grid_for_keys(nwords32 / 4) > 1024 ? 1024 : grid_for_keys(nwords32 / 4);
         hipLaunchKernelGGL(k_table_count, dim3(g), dim3(kBlock), 0, st, (const uint4 *)tab, nwords32 / 4, mode, d);
         e = hipGetLastError();
     }
@@ -2052,7 +1986,7 @@ extern "C" int psk_table_add_sat_i32(void *dst, const void *src, uint64_t n, int
     if (!dst || !src) return fail(PSK_EINVAL, "table pointer is NULL");
     PSK_USE_DEVICE(device);
     if (!n) return PSK_OK;
-    hipLaunchKernelGGL(k_add_sat_i32, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, (int32_t *)dst, (const int32_t *)src, n);
+    hipLaunchKernelGGL(k_add_sat_i32, dim3(grid_for_keys(n)), dim3(kBlock), 0, (hipStream_t)stream, (int32_t *)dst, (const int32_t *)src, n);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
 }
@@ -2066,7 +2000,7 @@ extern "C" int psk_table_add_u32(void *dst, const void *src, uint64_t n, uint64_
     HIP_TRY(hipMalloc((void **)&d, 8));
     hipError_t e = hipMemsetAsync(d, 0, 8, st);
     if (e == hipSuccess && n) {
-        hipLaunchKernelGGL(k_add_u32, dim3(grid_for(n)), dim3(kBlock), 0, st, (uint32_t *)dst, (const uint32_t *)src, n, d);
+        hipLaunchKernelGGL(k_add_u32, dim3(grid_for_keys(n)), dim3(kBlock), 0, st, (uint32_t *)dst, (const uint32_t *)src, n, d);
         e = hipGetLastError();
     }
     uint64_t ov = 0;
@@ -2087,7 +2021,7 @@ extern "C" int psk_cbf_intersect(void *dst, const void *a, const void *b, uint64
     HIP_TRY(hipMalloc((void **)&d, 8));
     hipError_t e = hipMemsetAsync(d, 0, 8, st);
     if (e == hipSuccess && n) {
-        const int g = grid_for(n) > 2048 ? 2048 : grid_for(n);
+        const int g = grid_for_keys(n) > 2048 ? 2048 : grid_for_keys(n);
         hipLaunchKernelGGL(k_cbf_intersect, dim3(g), dim3(kBlock), 0, st, (uint32_t *)dst, (const uint32_t *)a, (const uint32_t *)b, n, d);
         e = hipGetLastError();
     }
@@ -2109,7 +2043,7 @@ extern "C" int psk_cbf_jaccard_counts(const void *a, const void *b, uint64_t n, 
     HIP_TRY(hipMalloc((void **)&d, 16));
     hipError_t e = hipMemsetAsync(d, 0, 16, st);
     if (e == hipSuccess && n) {
-        const int g = grid_for(n) > 1024 ? 1024 : grid_for(n);
+        const int g = grid_for_keys(n) > 1024 ? 1024 : grid_for_keys(n);
         hipLaunchKernelGGL(k_cbf_jaccard, dim3(g), dim3(kBlock), 0, st, (const uint32_t *)a, (const uint32_t *)b, n, d);
         e = hipGetLastError();
     }
@@ -2125,12 +2059,11 @@ extern "C" int psk_scratch_bytes(psk_sketch *s, uint64_t bytes[3])
 {
     if (!s || !bytes) return fail(PSK_EINVAL, "psk_scratch_bytes: NULL argument");
     uint64_t all = 0, waiting = 0;
-    for (const DevBuf *b : {&s->s_keys, &s->s_offs, &s->s_w, &s->s_out, &s->s_aux, &s->s_part, &s->s_cnt, &s->s_flag, &s->s_spill, &s->s_tflag, &s->s_part2, &s->s_cnt2, &s->s_merge, &s->s_vals, &s->s_perm, &s->s_run, &s->s_tally,
-                            &s->comb.add.keys, &s->comb.add.w, &s->comb.rem.keys, &s->comb.rem.w, &s->scat.add.part, &s->scat.add.cnt, &s->scat.rem.part, &s->scat.rem.cnt, &s->s_brw, &s->shadow.img,
-                            &s->win.keys, &s->s_snap, &s->s_wstat, &s->s_phase})
-        if (b->p) all += b->cap;
-    for (const DevBuf *b : {&s->comb.add.keys, &s->comb.add.w, &s->comb.rem.keys, &s->comb.rem.w, &s->scat.add.part, &s->scat.add.cnt, &s->scat.rem.part, &s->scat.rem.cnt, &s->win.keys, &s->s_snap})
-        if (b->p) waiting += b->cap;
+    (void)for_each_scratch(s, [&](DevBuf &b, bool is_waiting) {
+        if (b.p) all += b.cap;
+        if (b.p && is_waiting) waiting += b.cap;
+        return (int)PSK_OK;
+    });
     bytes[0] = all;
     bytes[1] = waiting;
     bytes[2] = s->shadow.img.p ? s->shadow.img.cap : 0;
@@ -2146,13 +2079,12 @@ extern "C" int psk_release_scratch(psk_sketch *s)
     ho_apply(s);  // (what is waiting is applied under this sketch's own options)
     PSK_TRY(flush_combined(s, nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    for (DevBuf *b : {&s->s_keys, &s->s_offs, &s->s_w, &s->s_out, &s->s_aux, &s->s_part, &s->s_cnt, &s->s_flag, &s->s_spill, &s->s_tflag, &s->s_part2, &s->s_cnt2, &s->s_merge, &s->s_vals, &s->s_perm, &s->s_run, &s->s_tally,
-                      &s->comb.add.keys, &s->comb.add.w, &s->comb.rem.keys, &s->comb.rem.w, &s->scat.add.part, &s->scat.add.cnt, &s->scat.rem.part, &s->scat.rem.cnt, &s->s_brw, &s->shadow.img,
-                      &s->win.keys, &s->s_snap, &s->s_wstat, &s->s_phase}) {
-        if (b->p) HIP_TRY(hipFree(b->p));
-        b->p = nullptr;
-        b->cap = 0;
-    }
+    PSK_TRY(for_each_scratch(s, [](DevBuf &b, bool) {  // (the pinned pages stay: psk_destroy alone frees them)
+        if (b.p) HIP_TRY(hipFree(b.p));
+        b.p = nullptr;
+        b.cap = 0;
+        return (int)PSK_OK;
+    }));
     s->scat.ready = false;
     s->shadow.built = s->shadow.seen = ~0ULL;
     s->shadow.seen_count = 0;
@@ -2165,7 +2097,7 @@ extern "C" int psk_or_reduce_slices(void *dst, const void *src, uint32_t nslices
     if (nslices == 0) return fail(PSK_EINVAL, "nslices must be > 0");
     PSK_USE_DEVICE(device);
     if (!slice_words32) return PSK_OK;
-    hipLaunchKernelGGL(k_or_reduce, dim3(grid_for(slice_words32 / 4)), dim3(kBlock), 0, (hipStream_t)stream, (uint4 *)dst,
+    hipLaunchKernelGGL(k_or_reduce, dim3(grid_for_keys(slice_words32 / 4)), dim3(kBlock), 0, (hipStream_t)stream, (uint4 *)dst,
                        (const uint4 *)src, nslices, slice_words32 / 4);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
@@ -2177,7 +2109,7 @@ extern "C" int psk_gen_keys16(void *dst_dev, uint64_t start, uint64_t n, uint64_
     if (n && (!dst_dev || ((uintptr_t)dst_dev & 15))) return fail(PSK_EINVAL, "dst must be a 16-byte aligned device pointer");
     PSK_USE_DEVICE(device);
     if (!n) return PSK_OK;
-    hipLaunchKernelGGL(k_gen_keys16, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, (ulonglong2 *)dst_dev, start, n, seed);
+    hipLaunchKernelGGL(k_gen_keys16, dim3(grid_for_keys(n)), dim3(kBlock), 0, (hipStream_t)stream, (ulonglong2 *)dst_dev, start, n, seed);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
 }
@@ -2187,7 +2119,7 @@ extern "C" int psk_gen_weights(void *dst_dev, uint64_t start, uint64_t n, uint64
     if (n && !dst_dev) return fail(PSK_EINVAL, "dst is NULL");
     PSK_USE_DEVICE(device);
     if (!n) return PSK_OK;
-    hipLaunchKernelGGL(k_gen_weights, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, (int32_t *)dst_dev, start, n, seed);
+    hipLaunchKernelGGL(k_gen_weights, dim3(grid_for_keys(n)), dim3(kBlock), 0, (hipStream_t)stream, (int32_t *)dst_dev, start, n, seed);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
 }
@@ -2200,7 +2132,7 @@ extern "C" int psk_gups(void *table_dev, uint64_t nwords32, uint64_t n, int op, 
     PSK_USE_DEVICE(device);
     if (!n) return PSK_OK;
     hipStream_t st = (hipStream_t)stream;
-    dim3 g(grid_for(n)), blk(kBlock);
+    dim3 g(grid_for_keys(n)), blk(kBlock);
     if (op == 0) hipLaunchKernelGGL((k_gups<0>), g, blk, 0, st, (uint32_t *)table_dev, nwords32, n, seed, (unsigned long long *)sink_dev);
     else if (op == 1) hipLaunchKernelGGL((k_gups<1>), g, blk, 0, st, (uint32_t *)table_dev, nwords32, n, seed, (unsigned long long *)sink_dev);
     else if (op == 2) hipLaunchKernelGGL((k_gups<2>), g, blk, 0, st, (uint32_t *)table_dev, nwords32, n, seed, (unsigned long long *)sink_dev);

@@ -166,9 +166,9 @@ struct psk_sketch {
     };
     struct {
         bool ready = false;
-        PartGeom g{};        // the fixed geometry of both lists (nbuckets, shift, nwg, segcap, k; append = 1)
-        uint64_t cap = 0;    // keys per list the segments were sized for
-        ScatList add, rem;
+        PartGeom g{};        // the fixed geometry of the list (nbuckets, shift, nwg, segcap, k; append = 1)
+        uint64_t cap = 0;    // keys the segments were sized for
+        ScatList add;        // unit-weight adds only: they commute, so the probes may wait
         hipEvent_t ev = nullptr;       // recorded behind the last append (either mechanism): a flush on ANOTHER stream waits for it
         hipStream_t last = nullptr;
         bool appended = false;
@@ -792,7 +792,7 @@ PSK_HIDDEN int flush_combined(psk_sketch *s, hipStream_t st);  // apply the writ
 PSK_HIDDEN int clear_materialize(psk_sketch *s, hipStream_t st);  // run the deferred clear of a Bloom table now, if one is pending (psk_capi.hip)
 // pass 1 of a unit-weight CBF batch, appended to the handle's persistent add (neg = 0) / decrement (neg = 1) list; *done = false:
 // the batch / table is not eligible (nothing was launched)
-PSK_DECLARE_VARIANTS(int, cbf_scat_append, (psk_sketch *s, const Batch &b, int neg, hipStream_t st, bool *done))
+PSK_DECLARE_VARIANTS(int, cbf_scat_append, (psk_sketch *s, const Batch &b, hipStream_t st, bool *done))
 // unit-weight add (neg = 0) / unchecked decrement (neg = 1) of `n` borrowed 16-byte keys (device tables base[nb], start[nb + 1]) through the
 // nibble path; *done = false: table not eligible (nothing launched)
 PSK_DECLARE_VARIANTS(int, cbf_unit_multi_partitioned, (psk_sketch *s, const void *const *base_dev, const uint64_t *start_dev, uint32_t nb, uint64_t n, int neg, hipStream_t st, bool *done))

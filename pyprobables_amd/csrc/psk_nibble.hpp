@@ -362,37 +362,26 @@ __device__ __forceinline__ void nib_apply_list(uint32_t *smem, uint32_t *carried
     if (viol) atomicAdd(sat_ctr - 1, viol);
 }
 
-// MODE 0: the list is adds; 1: decrements; 2: list A adds, THEN list B decrements (one launch for a write-combined flush: the
-// slice a workgroup has just folded is still on-die when it folds it again).
+// MODE 0: the list is adds; 1: decrements.
 // direct != 0: atomics instead of the image, see nib_apply_list.
 template <int MODE>
-__global__ __launch_bounds__(kApplyThreads, 8) void k_nib_apply(uint32_t *tab, uint64_t tab_cells, PartGeom g, const uint32_t *segcnt_a, const uint4 *buckets_a,
-                                                             const uint32_t *segcnt_b, const uint4 *buckets_b, unsigned long long *sat_ctr, uint32_t direct,
-                                                             PartGeom gb)
+__global__ __launch_bounds__(kApplyThreads, 8) void k_nib_apply(uint32_t *tab, uint64_t tab_cells, PartGeom g, const uint32_t *segcnt, const uint4 *buckets,
+                                                             unsigned long long *sat_ctr, uint32_t direct)
 {
-    // gb: geometry of list B (MODE 2; same slices as g, its own workgroup count / segment capacity)
+    static_assert(MODE == 0 || MODE == 1, "k_nib_apply: adds or decrements");
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     __shared__ uint32_t carried;
     const uint32_t b = blockIdx.x;
     if (((uint64_t)b << g.shift) >= tab_cells) return;  // (a slice past the table's end)
-    if (MODE == 0 || MODE == 2) nib_apply_list<false>(smem, &carried, tab, tab_cells, g, segcnt_a, buckets_a, sat_ctr, b, direct != 0);
-    if (MODE == 2) {
-        __threadfence();   // my stores to the slice are visible to my loads below (same CU, but through L2: not the L1)
-        __syncthreads();
-    }
-    if (MODE == 1) nib_apply_list<true>(smem, &carried, tab, tab_cells, g, segcnt_a, buckets_a, sat_ctr, b, direct != 0);
-    if (MODE == 2) nib_apply_list<true>(smem, &carried, tab, tab_cells, gb, segcnt_b, buckets_b, sat_ctr, b, direct != 0);
+    nib_apply_list<MODE == 1>(smem, &carried, tab, tab_cells, g, segcnt, buckets, sat_ctr, b, direct != 0);
 }
 
 
-// segcnt[] of a persistent list back to zero after a flush (one launch for both lists)
-static __global__ __launch_bounds__(256) void k_zero_u32(uint32_t *a, uint64_t na, uint32_t *b, uint64_t nb)
+// segcnt[] of a persistent list back to zero after a flush
+static __global__ __launch_bounds__(256) void k_zero_u32(uint32_t *a, uint64_t n)
 {
     const uint64_t stride = (uint64_t)gridDim.x * 256;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < na + nb; i += stride) {
-        if (i < na) a[i] = 0;
-        else b[i - na] = 0;
-    }
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) a[i] = 0;
 }
 
 }  // namespace psk
