@@ -124,7 +124,8 @@ int psk_device_count(int *count);
  * "lookup_half_slices", "remove_optimistic", "lookup_nibble_slices", "update_nibble_slices", "nibble_min_lg_lookup", "nibble_min_lg_update",
  * "update_window_tile", "update_window_wide", "update_window_force_fail", "ragged_sort", "host_poll_us" (how long a tiny PSK_HOST call
  * polls its completion mailbox before it waits for the stream; 0 = never poll); read-only counters "cbf_ordered_replays",
- * "update_window_folds", "update_window_replays", "cms_small_weights_used", "cbf_lookup_shadow_hits".
+ * "update_window_folds", "update_window_replays", "cms_small_weights_used", "cbf_lookup_shadow_hits", "cms_running_fast",
+ * "cms_running_sequential" (psk_cms_add_running calls that took the parallel passes / the one-lane kernel).
  * The bench build (-DPSK_BENCH_KNOBS=1, libpsk_hip_knobs.so) has one more option, "part_debug": the ablation / phase-profile bits of the
  * measuring tools; this library answers "unknown option" to it.  The A/B switches of experiments that were measured and dropped are gone
  * with their code (NOTES.md). */
@@ -278,6 +279,19 @@ int psk_cms_check_meanmin(psk_sketch *s, int layout, const void *data, const uin
 int psk_cms_update_ordered(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n,
                            uint32_t key_len, const int64_t *weights, int opmode, int query,
                            int64_t elements_added_in, int where, int64_t *out, void *stream);
+/* countminsketch.py:267-288 for a whole ORDERED batch of adds at once: out[i] is what the reference's add(key_i, w_i) returns at its place
+ * in the stream under `query` (int32[n]; int64[n] for PSK_Q_MEANMIN), the table, *els_out = elements_added and the PSK_CTR_SATURATED /
+ * PSK_CTR_ABS_BOUND tallies end as the loop `for i: add(key_i, w_i)` leaves them.  weights: int32[n] >= 0 or NULL (= 1).  With w >= 0 a
+ * bin's value after op i is the saturating sum of the weights that reached it so far, a segmented scan in arrival order per (row, bin): a
+ * stable radix sort by bin per row, the scan, a per-op query -- a fixed number of streaming passes over ordered chunks of at most 2^20 ops
+ * (the scratch does not grow with n).  Tables with depth > 64 or width > 2^32 walk the batch on one lane (psk_cms_update_ordered's kernel)
+ * instead; read-only options "cms_running_fast" / "cms_running_sequential" count the calls either way.  A negative weight in a PSK_HOST
+ * batch is PSK_EINVAL before the table changes; in a PSK_DEVICE batch (enqueue only: out, els_out are device pointers) it is the caller's
+ * to exclude -- it counts as 0 and is tallied in PSK_CTR_VIOLATIONS. */
+int psk_cms_add_running(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n,
+                        uint32_t key_len, const int32_t *weights /* NULL = 1 */, int where, int query,
+                        int64_t els_in, void *out /* int32[n]; int64[n] for PSK_Q_MEANMIN */,
+                        int64_t *els_out, void *stream);
 
 /* ------------------------------------------------------------------ hashing
  * out[i*depth + j] = fnv_1a(key_i, seed=j)  (hashes.py:71-103); layout != PSK_KEYS_HASHES */

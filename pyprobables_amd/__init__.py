@@ -2,13 +2,13 @@
 
 Drop-in names for the accelerated path (reference ``probables/__init__.py:3-53``):
 ``BloomFilter``, ``CountingBloomFilter``, ``CountMinSketch`` (+ ``CountMeanSketch`` /
-``CountMeanMinSketch``), ``ExpandingBloomFilter`` / ``RotatingBloomFilter``, their exceptions and the ``hash_function`` helpers.  Tables live in GPU HBM,
+``CountMeanMinSketch``, ``HeavyHitters``, ``StreamThreshold``), ``ExpandingBloomFilter`` / ``RotatingBloomFilter``, their exceptions and the ``hash_function`` helpers.  Tables live in GPU HBM,
 the work is done by hand-written gfx950 HIP kernels behind the C ABI in ``include/psk.h``.
 """
 
 from .bloom import BloomFilter
 from .countingbloom import CountingBloomFilter
-from .countminsketch import CountMeanMinSketch, CountMeanSketch, CountMinSketch
+from .countminsketch import CountMeanMinSketch, CountMeanSketch, CountMinSketch, HeavyHitters, StreamThreshold
 from .expandingbloom import ExpandingBloomFilter, RotatingBloomFilter
 from .exceptions import (
     CountMinSketchError,
@@ -29,6 +29,8 @@ __all__ = [
     "CountMinSketch",
     "CountMeanSketch",
     "CountMeanMinSketch",
+    "HeavyHitters",
+    "StreamThreshold",
     "ExpandingBloomFilter",
     "RotatingBloomFilter",
     "RotatingBloomFilterError",

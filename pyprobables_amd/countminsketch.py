@@ -4,11 +4,16 @@ HBM and add / remove / check as fused HIP kernels.
 Drop-in for the hot path of ``probables.CountMinSketch`` (``probables/countminsketch/countminsketch.py``).
 Single-key ``add`` / ``remove`` run the reference semantics literally (ordered kernel: exact return value,
 exact int32 / int64 clamps); ``add_many`` / ``remove_many`` are unordered atomic batches whose final table is
-bit-exact whenever it does not depend on the order (same-sign weights, or no bin touching a rail).
+bit-exact whenever it does not depend on the order (same-sign weights, or no bin touching a rail);
+``add_many_ordered`` is the batch form of ``add``: what the reference's loop returns for every key of an ordered batch.
+
+``StreamThreshold`` and ``HeavyHitters`` (countminsketch.py:532-843) track a dict that every ``add`` feeds with its return value;
+their ``add_many`` is ``add_many_ordered`` plus the dict rule, written as the two pure functions ``threshold_rule`` / ``hitters_rule``.
 """
 
 from __future__ import annotations
 
+import ctypes as C
 import math
 import struct
 from io import BytesIO, IOBase
@@ -21,7 +26,7 @@ import numpy as np
 from . import _native as N
 from ._base import DeviceTable, weights_arg
 from .bloom import _existing_file, _torch_dtype
-from .exceptions import CountMinSketchError, InitializationError
+from .exceptions import CountMinSketchError, InitializationError, NotSupportedError
 from .hashes import HashFuncT, HashResultsT, KeyT, default_fnv_1a, device_digest, is_fused_fnv
 from .keys import KeyBatch, digest_batch, one_key_bytes, pack_hashes, pack_keys
 
@@ -322,6 +327,46 @@ class CountMinSketch:
     def remove_many(self, keys, num_els=None) -> None:
         self._update_batch(N.lib().psk_cms_remove, self._batch(keys), num_els)
 
+    def _add_running(self, b: KeyBatch, num_els):
+        """``psk_cms_add_running``: every op's return value of the ordered batch, on the batch's side"""
+        w = num_els
+        if w is not None:
+            if hasattr(w, "is_cuda"):  # a torch tensor (a device one costs one small reduction and a synchronisation here)
+                neg = bool(w.numel()) and int(w.min().item()) < 0
+            else:
+                a = np.asarray(w)
+                neg = bool(a.size) and int(a.min()) < 0
+            if neg:
+                raise ValueError("add_many_ordered: num_els must be >= 0 (removes are not part of an ordered add batch)")
+        keep: list = []
+        w_addr, _ = weights_arg(w, b.n, np.int32, b.where, keep, 0, _I32_MAX, self._tab.device)
+        wide = self._query == "mean-min"
+        addr, fin = self._tab.out_buffer(b, b.n, np.int64 if wide else np.int32, _torch_dtype("int64" if wide else "int32"))
+        els_in = self.elements_added
+        if b.where == N.DEVICE:
+            import torch  # noqa: PLC0415
+
+            els = torch.empty(1, dtype=torch.int64, device=f"cuda:{self._tab.device}")
+            els_addr = els.data_ptr()
+        else:
+            els = C.c_int64(0)
+            els_addr = C.addressof(els)
+        N.check(N.lib().psk_cms_add_running(self._tab.handle, *b.args(), w_addr, b.where, _QUERIES[self._query], els_in, addr or None, els_addr,
+                                            self._tab.stream))
+        self._els_added = int(els.item()) if b.where == N.DEVICE else els.value
+        return fin()
+
+    def add_many_ordered(self, keys, num_els=None):
+        """the batch form of ``add`` (countminsketch.py:257-288): the table and ``elements_added`` end as the loop
+        ``for key, w in zip(keys, num_els): add(key, w)`` leaves them and entry i of the result is what that loop's i-th ``add`` returns
+        under the current ``query_type`` -- int32 (int64 for 'mean-min'), numpy for host batches, a torch tensor for device batches.
+        ``keys`` / ``num_els`` as for ``add_many``; ``num_els`` must be >= 0 (ValueError before anything changes)."""
+        return self._add_running(self._batch(keys), num_els)
+
+    def add_alt_many_ordered(self, hashes, num_els=None):
+        """``add_many_ordered`` for pre-computed hashes (a (n, depth) uint64 array / tensor)"""
+        return self._add_running(self._alt(hashes), num_els)
+
     def add_alt_many(self, hashes, num_els=None) -> None:
         self._update_batch(N.lib().psk_cms_add, self._alt(hashes), num_els)
 
@@ -363,3 +408,226 @@ class CountMeanMinSketch(CountMinSketch):
     """default query 'mean-min' (countminsketch.py:494-529)"""
 
     _DEFAULT_QUERY = "mean-min"
+
+
+# ------------------------------------------------------------------ the tracked dicts of StreamThreshold / HeavyHitters
+def threshold_rule(tracked: dict, keys, results, threshold: int) -> dict:
+    """StreamThreshold's rule (countminsketch.py:800-803) over an ordered batch of adds: ``tracked[key] = res`` for every op with
+    ``res >= threshold``, in op order (a later store overwrites an earlier one and keeps the key's place).  ``keys`` / ``results``: the
+    ops that matter, or all of them.  Pure host code: dict in, the same dict out."""
+    tracked.update((k, int(r)) for k, r in zip(keys, results) if r >= threshold)
+    return tracked
+
+
+def hitters_rule(state, keys, results, num_hitters: int):
+    """HeavyHitters' rule (countminsketch.py:643-661) replayed in op order.  ``state`` = (top_x dict, smallest); returns the new state.
+    An op that meets a full list, a key that is not tracked and ``res <= smallest`` changes nothing -- the common case of a long stream,
+    one dict lookup and one compare here."""
+    top, smallest = state
+    get = top.get
+    for key, res in zip(keys, results):
+        res = int(res)
+        if len(top) < num_hitters:  # still have room (:646-650; __top_x_size is len(top) at every point the rule reads it)
+            top[key] = res
+        elif key in top:            # :651-652
+            top[key] = res
+        elif res > smallest:        # :653-660 something in there is smaller
+            top[key] = res
+            top.pop(min(top, key=get), None)
+            smallest = top[min(top, key=get)]
+    return top, smallest
+
+
+def _batch_keys(keys):
+    """the dict keys of a batch: the caller's own str / bytes objects of a list, ``bytes`` for array / tensor batches; -> indexable"""
+    if isinstance(keys, (str, bytes, bytearray, memoryview)):
+        return [keys]
+    if isinstance(keys, tuple) and len(keys) == 2 and hasattr(keys[0], "dtype"):  # ragged (blob, offsets)
+        blob, offs = (x.cpu().numpy() if hasattr(x, "is_cuda") else np.asarray(x) for x in keys)
+        if blob.dtype.itemsize != 1:
+            raise TypeError("tracked keys of a (blob, offsets) batch: a uint8 blob")
+        raw, o = blob.tobytes(), offs.astype(np.int64)
+        return [raw[o[i]:o[i + 1]] for i in range(o.size - 1)]
+    if hasattr(keys, "is_cuda"):
+        keys = keys.cpu().numpy()
+    if isinstance(keys, np.ndarray):
+        a = np.ascontiguousarray(keys)
+        a = a.view(np.uint8).reshape(a.shape[0], -1)
+        raw, L = a.tobytes(), a.shape[1]
+        return [raw[i * L:(i + 1) * L] for i in range(a.shape[0])]
+    return keys if isinstance(keys, list) else list(keys)
+
+
+class StreamThreshold(CountMinSketch):
+    """the keys whose count reached ``threshold`` when they were added (countminsketch.py:694-843).
+
+    Args as the reference: threshold, width, depth, confidence, error_rate, filepath, hash_function; extra: device."""
+
+    def __init__(self, threshold=100, width=None, depth=None, confidence=None, error_rate=None, filepath=None,
+                 hash_function: HashFuncT | None = None, device=None):
+        super().__init__(width, depth, confidence, error_rate, filepath, hash_function, device)
+        self._threshold = threshold
+        self._meets: dict = {}
+
+    @classmethod
+    def frombytes(cls, b, threshold=100, hash_function: HashFuncT | None = None, device=None):
+        width, depth, _ = _FOOTER.unpack_from(bytes(b[-_FOOTER.size:]))
+        inst = cls(threshold=threshold, width=width, depth=depth, hash_function=hash_function, device=device)
+        inst._parse_bytes(bytes(b))
+        return inst
+
+    def __str__(self) -> str:
+        return f"Stream Threshold {super().__str__()}\n\tThreshold: {self.threshold}\n\tNumber Meeting Threshold: {len(self._meets)}"
+
+    @property
+    def meets_threshold(self) -> dict:
+        return self._meets
+
+    @property
+    def threshold(self) -> int:
+        return self._threshold
+
+    def clear(self) -> None:
+        super().clear()
+        self._meets = {}
+
+    def add(self, key, num_els: int = 1) -> int:
+        """countminsketch.py:775-785"""
+        res = super().add(key, num_els)
+        threshold_rule(self._meets, (key,), (res,), self._threshold)
+        return res
+
+    def add_alt(self, key, hashes: HashResultsT, num_els: int = 1) -> int:
+        """countminsketch.py:787-803 (key first: the reference's signature)"""
+        res = super().add_alt(hashes, num_els)
+        threshold_rule(self._meets, (key,), (res,), self._threshold)
+        return res
+
+    def _removed(self, key, res: int) -> int:  # :831-834
+        if res < self._threshold:
+            self._meets.pop(key, None)
+        else:
+            self._meets[key] = res
+        return res
+
+    def remove(self, key, num_els: int = 1) -> int:
+        """countminsketch.py:805-815"""
+        return self._removed(key, super().remove(key, num_els))
+
+    def remove_alt(self, key, hashes: HashResultsT, num_els: int = 1) -> int:
+        """countminsketch.py:817-835"""
+        return self._removed(key, super().remove_alt(hashes, num_els))
+
+    def add_many(self, keys, num_els=None):
+        """``add`` for every key of the ordered batch: the sketch through ``add_many_ordered``; of the results only those that reached
+        the threshold matter to the dict -- they are selected where the results lie and stored in op order.  Returns the results."""
+        res = self.add_many_ordered(keys, num_els)
+        if hasattr(res, "is_cuda"):
+            import torch  # noqa: PLC0415
+
+            at = torch.nonzero(res >= self._threshold).flatten()
+            idx, vals = at.cpu().numpy(), res[at].cpu().numpy()
+        else:
+            idx = np.nonzero(res >= self._threshold)[0]
+            vals = res[idx]
+        if idx.size:
+            if isinstance(keys, list):
+                picked = [keys[i] for i in idx.tolist()]
+            elif hasattr(keys, "is_cuda") and keys.is_cuda:  # only the selected rows leave the device
+                import torch  # noqa: PLC0415
+
+                picked = _batch_keys(keys[torch.from_numpy(idx).to(keys.device)])
+            else:
+                allk = _batch_keys(keys)
+                picked = [allk[i] for i in idx.tolist()]
+            threshold_rule(self._meets, picked, vals.tolist(), self._threshold)
+        return res
+
+    def remove_many(self, keys, num_els=None):
+        """``remove`` for every key of an ordered HOST batch.  Exact and slow: the removes walk the batch on one lane
+        (``update_ordered``'s sequential kernel); there is no parallel ordered remove."""
+        allk = _batch_keys(keys)
+        res = self._ordered(self._batch(keys), 1 if num_els is None else num_els, N.OP_REMOVE)
+        for key, r in zip(allk, res.tolist()):
+            self._removed(key, r)
+        return res
+
+    def join(self, second) -> None:
+        raise NotSupportedError("Joining is not supported for stream threshold")
+
+
+class HeavyHitters(CountMinSketch):
+    """the ``num_hitters`` most common keys seen so far (countminsketch.py:532-691).
+
+    Args as the reference: num_hitters, width, depth, confidence, error_rate, filepath, hash_function; extra: device."""
+
+    def __init__(self, num_hitters=100, width=None, depth=None, confidence=None, error_rate=None, filepath=None,
+                 hash_function: HashFuncT | None = None, device=None):
+        super().__init__(width, depth, confidence, error_rate, filepath, hash_function, device)
+        self._top: dict = {}
+        self._num_hitters = num_hitters
+        self._smallest = 0
+
+    @classmethod
+    def frombytes(cls, b, num_hitters=100, hash_function: HashFuncT | None = None, device=None):
+        width, depth, _ = _FOOTER.unpack_from(bytes(b[-_FOOTER.size:]))
+        inst = cls(num_hitters=num_hitters, width=width, depth=depth, hash_function=hash_function, device=device)
+        inst._parse_bytes(bytes(b))
+        return inst
+
+    def __str__(self) -> str:
+        return f"Heavy Hitters {super().__str__()}\n\tNumber Hitters: {self.number_heavy_hitters}\n\tNumber Recorded: {len(self._top)}"
+
+    @property
+    def heavy_hitters(self) -> dict:
+        return self._top
+
+    @property
+    def number_heavy_hitters(self) -> int:
+        return self._num_hitters
+
+    def _track(self, keys, results) -> None:
+        self._top, self._smallest = hitters_rule((self._top, self._smallest), keys, results, self._num_hitters)
+
+    def add(self, key, num_els: int = 1) -> int:
+        """countminsketch.py:617-627"""
+        res = super().add(key, num_els)
+        self._track((key,), (res,))
+        return res
+
+    def add_alt(self, key, hashes: HashResultsT, num_els: int = 1) -> int:
+        """countminsketch.py:629-661 (key first: the reference's signature)"""
+        res = super().add_alt(hashes, num_els)
+        self._track((key,), (res,))
+        return res
+
+    def add_many(self, keys, num_els=None):
+        """``add`` for every key of the ordered batch: the sketch through ``add_many_ordered``, then the list rule replayed in op
+        order on the host.  Returns the results."""
+        res = self.add_many_ordered(keys, num_els)
+        self._track(_batch_keys(keys), (res.cpu().numpy() if hasattr(res, "is_cuda") else res).tolist())
+        return res
+
+    _NO_REMOVE = ("Unable to remove elements in the HeavyHitters "
+                  "class as it is an un supported action (and does not"
+                  "make sense)!")
+
+    def remove(self, key, num_els: int = 1):
+        raise NotSupportedError(self._NO_REMOVE)
+
+    def remove_alt(self, *args, **kwargs):
+        """countminsketch.py:663-676"""
+        raise NotSupportedError(self._NO_REMOVE)
+
+    def remove_many(self, keys, num_els=None):
+        raise NotSupportedError(self._NO_REMOVE)
+
+    remove_alt_many = remove_many
+
+    def clear(self) -> None:
+        super().clear()
+        self._top = {}
+        self._smallest = 0
+
+    def join(self, second) -> None:
+        raise NotSupportedError("Joining is not supported for heavy hitters")

@@ -4,6 +4,7 @@
 #include "psk_digest.hpp"
 #include "psk_nibble.hpp"
 #include "psk_window.hpp"
+#include "psk_running.hpp"
 
 #include <chrono>
 #include <map>
@@ -650,6 +651,7 @@ int64_t g_lookup_nibble = 1;   // CBF lookups into 2^25 .. 2^29 counters: 4-bit 
 int64_t g_small_weights_used = 0;
 int64_t g_small_weights = 1;   // PayWeightSmall for weighted CountMinSketch adds (psk_sketch::wt)
 int64_t g_cbf_shadow_hits = 0;
+int64_t g_running_fast = 0, g_running_sequential = 0;   // psk_cms_add_running calls that took the parallel passes / the one-lane kernel (read-only options)
 __thread int64_t g_cbf_shadow = 1;  // nibble-slice lookups keep their 4-bit images while the table is unchanged (psk_sketch::shadow; cells / 2 bytes)
 int64_t g_nib_min_lg_lookup = 23, g_nib_min_lg_update = 24;  // see nib_geometry (psk_host.hpp); measured crossovers: scripts/ab_nib_threshold.py
 int64_t g_ragged_sort = 1;    // pass 1's per-tile length sort of ragged keys (A/B: 0 = batch order); option "ragged_sort"
@@ -709,6 +711,8 @@ const OptDesc kOptions[] = {
     {"update_window_replays", &g_window_replays, kOptReadOnly, kAny},
     {"cms_small_weights_used", &g_small_weights_used, kOptReadOnly, kAny},
     {"cbf_lookup_shadow_hits", &g_cbf_shadow_hits, kOptReadOnly, kAny},
+    {"cms_running_fast", &g_running_fast, kOptReadOnly, kAny},
+    {"cms_running_sequential", &g_running_sequential, kOptReadOnly, kAny},
     // measuring tools (bench builds only)
     {"part_debug", &g_part_debug, kOptKnob, kAny},
 };
@@ -1866,6 +1870,80 @@ extern "C" int psk_cms_update_ordered(psk_sketch *s, int layout, const void *dat
         });
     }));
     return finish(where, &o, st, &mb);
+}
+
+// countminsketch.py:267-288 for a whole ordered batch of adds: the table, elements_added and EVERY op's return value as the reference's loop
+// leaves them.  The parallel passes of psk_running.hpp wherever they apply (depth <= kMaxDepthMeanMin, width <= 2^32; weights >= 0 is the
+// entry's contract), else k_cms_ordered: always exact.  Which one ran: read-only options "cms_running_fast" / "cms_running_sequential".
+extern "C" int psk_cms_add_running(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len,
+                                   const int32_t *weights, int where, int query, int64_t els_in, void *out, int64_t *els_out, void *stream)
+{
+    CHECK_HANDLE(s, PSK_KIND_CMS);
+    PSK_TRY(check_hashes_width(s, layout, key_len));
+    if (query < PSK_Q_MIN || query > PSK_Q_MEANMIN) return fail(PSK_EINVAL, "bad query %d", query);
+    if (query == PSK_Q_MEANMIN && s->m < 2) return fail(PSK_EINVAL, "mean-min query needs width >= 2");
+    if (n && !out) return fail(PSK_EINVAL, "out is NULL");
+    if (where == PSK_HOST && weights)
+        for (uint64_t i = 0; i < n; ++i)
+            if (weights[i] < 0) return fail(PSK_EINVAL, "ordered add: weight %d of op %llu is negative", weights[i], (unsigned long long)i);
+    hipStream_t st = (hipStream_t)stream;
+    Batch b;
+    PSK_TRY(stage_batch(s->s_keys, s->s_offs, layout, data, offsets, n, key_len, where, st, &b));
+    if (n == 0) {
+        if (els_out && where == PSK_HOST) *els_out = els_in;
+        else if (els_out) {
+            hipLaunchKernelGGL(k_run_set, dim3(1), dim3(1), 0, st, (long long *)els_out, (long long)els_in);
+            HIP_TRY(hipGetLastError());
+        }
+        return PSK_OK;
+    }
+    const int32_t *w;
+    PSK_TRY(stage_vec(s->s_w, weights, n, where, st, &w));
+    const bool wide_out = query == PSK_Q_MEANMIN;
+    OutBuf o;
+    PSK_TRY(stage_out(s->s_out, out, n * (wide_out ? 8 : 4), where, &o));
+    // elements_added behind the batch: a device word; a host caller gets it copied back in front of the wait in finish()
+    PSK_TRY(ensure(s->s_aux, 8ULL * (s->k > (uint32_t)kMaxDepthMeanMin ? s->k : 1u) + 8));
+    int64_t *els_dev = where == PSK_DEVICE && els_out ? els_out : (int64_t *)s->s_aux.p;
+    if (s->k <= (uint32_t)kMaxDepthMeanMin && s->m <= (1ULL << 32)) {
+        __atomic_add_fetch(&g_running_fast, 1, __ATOMIC_RELAXED);
+        RunArena a;
+        PSK_TRY(cms_running_arena(s, n, &a));
+        for (uint64_t base = 0; base < n; base += a.cap) {
+            const uint32_t nc = (uint32_t)(n - base < a.cap ? n - base : a.cap);
+            PSK_TRY(with_source(b, [&](auto src) {
+                return with_pow2(s, [&](auto P) {
+                    hipLaunchKernelGGL((k_run_hash<decltype(src), P.value>), dim3(grid_for_keys(nc)), dim3(kBlock), 0, st, src, s->md, s->k, base, nc, a.cap, a.bins);
+                    HIP_TRY(hipGetLastError());
+                    return (int)PSK_OK;
+                });
+            }));
+            PSK_TRY(cms_running_chunk(s, a, w, base, nc, base == 0, els_in, query, o.dev, els_dev, st));
+        }
+    } else {  // one lane, one op after the other (int64 weights and results: widened / narrowed around it)
+        __atomic_add_fetch(&g_running_sequential, 1, __ATOMIC_RELAXED);
+        int64_t *wide = nullptr;
+        if (s->k > (uint32_t)kMaxDepthMeanMin) wide = (int64_t *)s->s_aux.p + 1;
+        PSK_TRY(ensure(s->s_perm, 8 * (n + 1)));
+        const int64_t *w64 = nullptr;
+        if (w) {
+            PSK_TRY(ensure(s->s_vals, 8 * n));
+            hipLaunchKernelGGL(k_run_widen, dim3(grid_for_keys(n)), dim3(kBlock), 0, st, w, n, (int64_t *)s->s_vals.p);
+            w64 = (const int64_t *)s->s_vals.p;
+        }
+        PSK_TRY(with_source(b, [&](auto src) {
+            return with_pow2(s, [&](auto P) {
+                hipLaunchKernelGGL((k_cms_ordered<decltype(src), P.value>), dim3(1), dim3(64), 0, st, src, (int32_t *)s->table, s->md, s->k, w64, (int)PSK_OP_ADD, query,
+                                   els_in, n, (int64_t *)s->s_perm.p, s->ctr, wide, (uint32_t *)nullptr, 0u);
+                HIP_TRY(hipGetLastError());
+                return (int)PSK_OK;
+            });
+        }));
+        hipLaunchKernelGGL(k_run_narrow, dim3(grid_for_keys(n)), dim3(kBlock), 0, st, (const int64_t *)s->s_perm.p, n, wide_out ? 1 : 0, o.dev, (long long *)els_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    if (where == PSK_HOST && els_out) HIP_TRY(hipMemcpyAsync(els_out, els_dev, 8, hipMemcpyDeviceToHost, st));
+    return finish(where, &o, st);
 }
 
 // ------------------------------------------------------------------ hashing
