@@ -304,6 +304,38 @@ enum psk_digest { PSK_DIGEST_MD5 = 0, PSK_DIGEST_SHA256 = 1 };
 int psk_digest_chain(int algo, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len,
                      uint32_t depth, int where, uint64_t *out, int device, void *stream);
 
+/* ------------------------------------------------------------ QuotientFilter
+ * quotientfilter.py: a table of 2^q slots (3 <= q <= 31) for 32-bit hashes, quotient = h >> r, remainder = h & (2^r - 1), r = 32 - q.
+ * No handle: the caller owns the four arrays (device memory) --
+ *   filter        remainders, uint8 / uint16 / uint32 per slot for r <= 8 / r <= 16 / else (the reference's array type codes B / I / L)
+ *   occupied, continuation, shifted   bit arrays, LSB first in 32-bit words, max(2^q / 32, 1) words each
+ * The reference drops duplicates and keeps runs sorted, so its table depends only on the SET of hashes inserted; every call below
+ * produces or reads exactly that table (DESIGN.md "Quotient filter").  Removal (quotientfilter.py:168-185) is not offered.
+ *   hash       out[i] = fnv_1a_32(key_i, 0) (hashes.py:106-122: add / check hash this way); `where` as everywhere (out follows the keys);
+ *              PSK_KEYS_HASHES rows give the low 32 bits of their first hash
+ *   build      the table of the n SORTED DISTINCT hashes (n <= 2^q; sorting and deduplicating is the caller's -- any radix sort), written
+ *              over whatever the arrays held: what `for h in hashes: add_alt(h)` leaves (quotientfilter.py:154-166, :291-394) for any
+ *              order and any duplicates.  scratch_dev: n / 1024 + 2 int32.  Enqueue only.
+ *   check      out[i] = 0 / 1, check(key_i) (quotientfilter.py:187-206, :471-491); check_alt: the same for device uint32 hashes
+ *   decode     the table's hashes in slot order (ascending up to a rotation; sort for the ascending list), two passes around the
+ *              caller's prefix sums: out_dev NULL -> word_counts_dev[3][words] (int64) receives per metadata word the run starts, occupied
+ *              bits and slots in use, marks_dev[0] the first slot with continuation = shifted = 0, marks_dev[1] the first empty slot
+ *              (0xFFFFFFFF: full table; quotientfilter.py:215-218 starts hashes() there); the caller turns each row into INCLUSIVE
+ *              prefix sums in place and calls again with out_dev (uint32[out_cap], out_cap >= the last entry of row 2: the element
+ *              count) (quotientfilter.py:208-245 hashes / get_hashes).  Enqueue only. */
+int psk_qf_hash(int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, uint32_t *out,
+                int device, void *stream);
+int psk_qf_build(uint32_t q, const uint32_t *sorted_hashes_dev, uint64_t n, void *filter_dev, uint32_t *occupied_dev,
+                 uint32_t *continuation_dev, uint32_t *shifted_dev, int32_t *scratch_dev, int device, void *stream);
+int psk_qf_check(uint32_t q, const void *filter_dev, const uint32_t *occupied_dev, const uint32_t *continuation_dev,
+                 const uint32_t *shifted_dev, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len,
+                 int where, uint8_t *out, int device, void *stream);
+int psk_qf_check_alt(uint32_t q, const void *filter_dev, const uint32_t *occupied_dev, const uint32_t *continuation_dev,
+                     const uint32_t *shifted_dev, const uint32_t *hashes_dev, uint64_t n, uint8_t *out_dev, int device, void *stream);
+int psk_qf_decode(uint32_t q, const void *filter_dev, const uint32_t *occupied_dev, const uint32_t *continuation_dev,
+                  const uint32_t *shifted_dev, int64_t *word_counts_dev, uint32_t *marks_dev, uint32_t *out_dev, uint64_t out_cap,
+                  int device, void *stream);
+
 /* ------------------------------------------------------ table algebra (device pointers)
  * Streaming kernels over whole tables; also the local half of the multi-GPU merge.
  * or/and: bloom.py:371-428 union/intersection;  popcount: bloom.py:552-557;

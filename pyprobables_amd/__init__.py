@@ -2,7 +2,7 @@
 
 Drop-in names for the accelerated path (reference ``probables/__init__.py:3-53``):
 ``BloomFilter``, ``CountingBloomFilter``, ``CountMinSketch`` (+ ``CountMeanSketch`` /
-``CountMeanMinSketch``, ``HeavyHitters``, ``StreamThreshold``), ``ExpandingBloomFilter`` / ``RotatingBloomFilter``, their exceptions and the ``hash_function`` helpers.  Tables live in GPU HBM,
+``CountMeanMinSketch``, ``HeavyHitters``, ``StreamThreshold``), ``ExpandingBloomFilter`` / ``RotatingBloomFilter``, ``QuotientFilter``, their exceptions and the ``hash_function`` helpers.  Tables live in GPU HBM,
 the work is done by hand-written gfx950 HIP kernels behind the C ABI in ``include/psk.h``.
 """
 
@@ -16,10 +16,12 @@ from .exceptions import (
     NativeLibraryError,
     NotSupportedError,
     ProbablesBaseException,
+    QuotientFilterError,
     RotatingBloomFilterError,
     SimilarityError,
 )
-from .hashes import default_fnv_1a, default_md5, default_sha256, fnv_1a, hash_with_depth_bytes, hash_with_depth_int
+from .quotientfilter import QuotientFilter
+from .hashes import default_fnv_1a, default_md5, default_sha256, fnv_1a, fnv_1a_32, hash_with_depth_bytes, hash_with_depth_int
 
 __version__ = "0.1.0"
 
@@ -33,6 +35,8 @@ __all__ = [
     "StreamThreshold",
     "ExpandingBloomFilter",
     "RotatingBloomFilter",
+    "QuotientFilter",
+    "QuotientFilterError",
     "RotatingBloomFilterError",
     "InitializationError",
     "NotSupportedError",
@@ -42,6 +46,7 @@ __all__ = [
     "NativeLibraryError",
     "default_fnv_1a",
     "fnv_1a",
+    "fnv_1a_32",
     "default_md5",
     "default_sha256",
     "hash_with_depth_bytes",

@@ -73,6 +73,11 @@ PROTOTYPES = {
     "psk_cms_add_running": (_int, [_vp, *_KEYS, _vp, _int, _int, _i64, _vp, _vp, _vp]),
     "psk_fnv1a_hash": (_int, [*_KEYS, _u32, _int, _vp, _int, _vp]),
     "psk_digest_chain": (_int, [_int, *_KEYS, _u32, _int, _vp, _int, _vp]),
+    "psk_qf_hash": (_int, [*_KEYS, _int, _vp, _int, _vp]),
+    "psk_qf_build": (_int, [_u32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
+    "psk_qf_check": (_int, [_u32, _vp, _vp, _vp, _vp, *_KEYS, _int, _vp, _int, _vp]),
+    "psk_qf_check_alt": (_int, [_u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _int, _vp]),
+    "psk_qf_decode": (_int, [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _int, _vp]),
     "psk_table_or": (_int, [_vp, _vp, _u64, _int, _vp]),
     "psk_table_and": (_int, [_vp, _vp, _u64, _int, _vp]),
     "psk_table_popcount": (_int, [_vp, _u64, C.POINTER(_u64), _int, _vp]),

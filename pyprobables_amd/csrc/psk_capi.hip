@@ -5,6 +5,7 @@
 #include "psk_nibble.hpp"
 #include "psk_window.hpp"
 #include "psk_running.hpp"
+#include "psk_quotient.hpp"
 
 #include <chrono>
 #include <map>
@@ -1964,6 +1965,55 @@ extern "C" int psk_fnv1a_hash(int layout, const void *data, const uint64_t *offs
         PSK_TRY(with_source(b, [&](auto src) {
             using Src = decltype(src);
             hipLaunchKernelGGL((k_hash<Src>), dim3(grid_for_keys(n)), dim3(kBlock), 0, st, src, (uint64_t *)o.dev, depth, n);
+            HIP_TRY(hipGetLastError());
+            return (int)PSK_OK;
+        }));
+    }
+    return finish(where, &o, st);
+}
+
+// ------------------------------------------------------------------ quotient filter: the calls that take KEYS (psk_quotient.hip holds the rest)
+// out[i] = fnv_1a_32(key_i, 0)  (hashes.py:106-122; quotientfilter.py:151 add, :194 check); PSK_KEYS_HASHES: the low half of each row's first hash
+extern "C" int psk_qf_hash(int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, uint32_t *out, int device,
+                           void *stream)
+{
+    if (layout == PSK_KEYS_HASHES && key_len < 1) return fail(PSK_EINVAL, "pre-hashed batch carries no hash per key");
+    if (n && !out) return fail(PSK_EINVAL, "out is NULL");
+    PSK_USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    Batch b;
+    PSK_TRY(stage_batch(g_hkeys, g_hoffs, layout, data, offsets, n, key_len, where, st, &b));
+    OutBuf o;
+    PSK_TRY(stage_out(g_hout, out, n * 4, where, &o));
+    if (n) {
+        PSK_TRY(with_source(b, [&](auto src) {
+            hipLaunchKernelGGL((k_qf_hash<decltype(src)>), dim3(grid_for_keys(n)), dim3(kBlock), 0, st, src, (uint32_t *)o.dev, n);
+            HIP_TRY(hipGetLastError());
+            return (int)PSK_OK;
+        }));
+    }
+    return finish(where, &o, st);
+}
+
+// out[i] = key_i's hash is in the table (quotientfilter.py:187-206 check / check_alt): hash and walk in one kernel
+extern "C" int psk_qf_check(uint32_t q, const void *filter_dev, const uint32_t *occupied_dev, const uint32_t *continuation_dev, const uint32_t *shifted_dev,
+                            int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, uint8_t *out, int device,
+                            void *stream)
+{
+    if (q < 3 || q > 31) return fail(PSK_EINVAL, "quotient must be between 3 and 31; %u was provided", q);
+    if (!filter_dev || !occupied_dev || !continuation_dev || !shifted_dev) return fail(PSK_EINVAL, "NULL table pointer");
+    if (layout == PSK_KEYS_HASHES && key_len < 1) return fail(PSK_EINVAL, "pre-hashed batch carries no hash per key");
+    if (n && !out) return fail(PSK_EINVAL, "out is NULL");
+    PSK_USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    Batch b;
+    PSK_TRY(stage_batch(g_hkeys, g_hoffs, layout, data, offsets, n, key_len, where, st, &b));
+    OutBuf o;
+    PSK_TRY(stage_out(g_hout, out, n, where, &o));
+    if (n) {
+        const QfTable t{filter_dev, occupied_dev, continuation_dev, shifted_dev, q};
+        PSK_TRY(with_source(b, [&](auto src) {
+            hipLaunchKernelGGL((k_qf_check<decltype(src)>), dim3(grid_for_keys(n)), dim3(kBlock), 0, st, src, t, (uint8_t *)o.dev, n);
             HIP_TRY(hipGetLastError());
             return (int)PSK_OK;
         }));

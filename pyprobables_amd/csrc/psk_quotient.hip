@@ -1,0 +1,290 @@
+// psk_quotient.hip -- quotient filter: bulk build, lookup of pre-computed hashes, decode (include/psk.h "QuotientFilter").
+//
+// Build (k_qf_tile_max / k_qf_tile_scan / k_qf_place).  For the sorted distinct hashes h_0 < h_1 < ..., quotients q_i = h_i >> r, the
+// reference's table stores element i at
+//     pos_i = max(q_i, pos_{i-1} + 1) = i + max_{j <= i} (q_j - j)                 (quotientfilter.py:291-394 _shift_insert / _add)
+// -- a prefix max over d_j = q_j - j, done as reduce (one max per tile of 1024), scan (the tile maxima, one workgroup), apply (each tile
+// rescans itself behind its carry).  When pos_{n-1} = n - 1 + max_j d_j reaches past the last slot the tail wraps and pushes the head: the
+// same recurrence with pos_{-1} = c = pos_{n-1} - size, i.e. pos_i = i + max(c + 1, max_{j <= i} d_j).  c + 1 is ONE constant known after
+// the scan, so the "second sweep" is a max inside the apply; it cannot move pos_{n-1} again while n <= size (c + 1 + n - 1 <= pos_{n-1}).
+// Metadata bits go into the zeroed table with word-level atomicOr: a lane's 4 elements land in ascending slots, so it gathers the bits of
+// one word in a register and issues an atomic only when the word changes (one per word it touches, not one per bit); lanes of neighbouring
+// elements share words, which is what the atomic resolves.  (One word per lane group without atomics would need the elements regrouped by
+// destination word -- a second scan over pos -- for the same 3 x size / 8 bytes written.)
+//
+// Decode (k_qf_decode_count / k_qf_decode_emit): run starts are slots with !continuation & (occupied | shifted); the k-th run start in
+// slot order belongs to the occupied quotient number (k - w) mod runs, where w = (run starts before x) - (occupied bits before x) for ANY
+// slot x with continuation = shifted = 0: an empty slot (the next run behind it belongs to the next occupied quotient) or a cluster start
+// (its run is its own quotient's).  Such a slot exists in every table, the full one included (the element with the largest q_j - j sits
+// in its own slot), so a full table decodes like any other.
+#include "psk_host.hpp"
+#include "psk_quotient.hpp"
+
+namespace {
+
+constexpr int kItems = 4;                      // consecutive elements per lane (one 16-byte load)
+constexpr uint32_t kTile = kBlock * kItems;    // elements per workgroup
+constexpr int32_t kNegInf = INT32_MIN;
+
+__device__ __forceinline__ int32_t wave_max(int32_t v)
+{
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+    return v;
+}
+
+// d_j = q_j - j fits int32: 0 <= q_j < 2^31, 0 <= j < 2^31
+__device__ __forceinline__ int32_t qf_d(uint32_t h, uint32_t rbits, uint64_t j) { return (int32_t)((int64_t)(h >> rbits) - (int64_t)j); }
+
+__global__ __launch_bounds__(kBlock) void k_qf_tile_max(const uint32_t *hs, uint64_t n, uint32_t rbits, int32_t *tile_max)
+{
+    __shared__ int32_t part[kBlock / 64];
+    const uint64_t base = (uint64_t)blockIdx.x * kTile;
+    int32_t m = kNegInf;
+    for (uint32_t e = threadIdx.x; e < kTile; e += kBlock) {
+        const uint64_t i = base + e;
+        if (i < n) m = max(m, qf_d(hs[i], rbits, i));
+    }
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kBlock / 64; ++w) m = max(m, part[w]);
+        tile_max[blockIdx.x] = m;
+    }
+}
+
+// tile_max[t] <- max of the tiles in front of t (exclusive), tile_max[ntiles] <- max of all; one workgroup
+__global__ __launch_bounds__(kBlock) void k_qf_tile_scan(int32_t *tile_max, uint32_t ntiles)
+{
+    __shared__ int32_t buf[kBlock];
+    int32_t carry = kNegInf;
+    for (uint32_t base = 0; base < ntiles; base += kBlock) {
+        const uint32_t t = base + threadIdx.x;
+        const int32_t mine = t < ntiles ? tile_max[t] : kNegInf;
+        int32_t v = mine;
+        buf[threadIdx.x] = v;
+        __syncthreads();
+        for (int o = 1; o < kBlock; o <<= 1) {
+            const int32_t other = (int)threadIdx.x >= o ? buf[threadIdx.x - o] : kNegInf;
+            __syncthreads();
+            v = max(v, other);
+            buf[threadIdx.x] = v;
+            __syncthreads();
+        }
+        const int32_t excl = max(carry, threadIdx.x ? buf[threadIdx.x - 1] : kNegInf);
+        if (t < ntiles) tile_max[t] = excl;
+        carry = max(carry, buf[kBlock - 1]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) tile_max[ntiles] = carry;
+}
+
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_qf_place(const uint32_t *hs, uint64_t n, uint32_t q, const int32_t *tile_carry, uint32_t ntiles, T *filter,
+                                                     uint32_t *occ, uint32_t *cont, uint32_t *sh)
+{
+    __shared__ int32_t wave_tot[kBlock / 64];
+    const uint32_t rbits = 32u - q, smask = (1u << q) - 1u, rmask = (1u << rbits) - 1u;
+    const uint64_t first = (uint64_t)blockIdx.x * kTile + (uint64_t)threadIdx.x * kItems;
+    uint32_t h[kItems];
+    int32_t run = kNegInf;  // max of d over this lane's elements
+#pragma unroll
+    for (int e = 0; e < kItems; ++e) {
+        h[e] = first + e < n ? hs[first + e] : 0u;
+        if (first + e < n) run = max(run, qf_d(h[e], rbits, first + e));
+    }
+    // exclusive prefix max over the lanes of the tile: inside the wave by shuffles, across the four waves through LDS
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    int32_t incl = run;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int32_t other = __shfl_up(incl, o);
+        if ((int)lane >= o) incl = max(incl, other);
+    }
+    if (lane == 63) wave_tot[wv] = incl;
+    __syncthreads();
+    int32_t m = tile_carry[blockIdx.x];
+    for (uint32_t x = 0; x < wv; ++x) m = max(m, wave_tot[x]);
+    const int32_t up = __shfl_up(incl, 1);
+    if (lane) m = max(m, up);
+
+    const int64_t size = (int64_t)smask + 1, last = (int64_t)n - 1 + tile_carry[ntiles];
+    const int64_t wrap = last >= size ? last - size + 1 : INT64_MIN;  // c + 1 of the wrapped tail, see above
+    uint32_t prev_q = first && first < n ? hs[first - 1] >> rbits : 0xFFFFFFFFu;
+    uint32_t mw = 0xFFFFFFFFu, cbits = 0, sbits = 0;  // metadata word being gathered
+    uint32_t ow = 0xFFFFFFFFu, obits = 0;
+#pragma unroll
+    for (int e = 0; e < kItems; ++e) {
+        const uint64_t i = first + e;
+        if (i >= n) break;
+        const uint32_t qi = h[e] >> rbits;
+        m = max(m, qf_d(h[e], rbits, i));
+        const int64_t mm = (int64_t)m > wrap ? (int64_t)m : wrap;
+        const uint32_t p = (uint32_t)((int64_t)i + mm) & smask;
+        filter[p] = (T)(h[e] & rmask);
+        if ((p >> 5) != mw) {
+            if (cbits) atomicOr(cont + mw, cbits);
+            if (sbits) atomicOr(sh + mw, sbits);
+            mw = p >> 5, cbits = sbits = 0;
+        }
+        if (qi == prev_q) cbits |= 1u << (p & 31u);
+        if (p != qi) sbits |= 1u << (p & 31u);
+        if ((qi >> 5) != ow) {
+            if (obits) atomicOr(occ + ow, obits);
+            ow = qi >> 5, obits = 0;
+        }
+        obits |= 1u << (qi & 31u);
+        prev_q = qi;
+    }
+    if (cbits) atomicOr(cont + mw, cbits);
+    if (sbits) atomicOr(sh + mw, sbits);
+    if (obits) atomicOr(occ + ow, obits);
+}
+
+__global__ __launch_bounds__(kBlock) void k_qf_check_alt(psk::QfTable t, const uint32_t *hashes, uint64_t n, uint8_t *out)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) out[i] = psk::qf_contains(t, hashes[i]) ? 1 : 0;
+}
+
+// ---- decode
+// per metadata word: run starts, occupied bits, slots in use (counts[0 / 1 / 2][w]); marks[0] = the first slot with continuation = shifted = 0
+// (the anchor x above), marks[1] = the first empty slot (0xFFFFFFFF: none, the table is full)
+__global__ __launch_bounds__(kBlock) void k_qf_decode_count(const uint32_t *occ, const uint32_t *cont, const uint32_t *sh, uint32_t nwords, uint32_t valid,
+                                                            long long *counts, uint32_t *marks)
+{
+    const uint32_t stride = gridDim.x * kBlock;
+    for (uint32_t w = blockIdx.x * kBlock + threadIdx.x; w < nwords; w += stride) {
+        const uint32_t o = occ[w] & valid, c = cont[w] & valid, s = sh[w] & valid;
+        counts[w] = __popc(~c & (o | s));
+        counts[(uint64_t)nwords + w] = __popc(o);
+        counts[2ull * nwords + w] = __popc(o | c | s);
+        const uint32_t anchor = ~(c | s) & valid, empty = ~(o | c | s) & valid;
+        if (anchor) atomicMin(marks, (w << 5) + (uint32_t)__ffs(anchor) - 1u);
+        if (empty) atomicMin(marks + 1, (w << 5) + (uint32_t)__ffs(empty) - 1u);
+    }
+}
+
+__device__ __forceinline__ long long excl(const long long *inc, uint32_t w) { return w ? inc[w - 1] : 0; }
+__device__ __forceinline__ uint32_t below(uint32_t bit) { return (1u << bit) - 1u; }  // bits 0 .. bit - 1
+
+// counts: the three rows above as INCLUSIVE prefix sums.  One lane per slot; a slot in use writes its hash at its rank among the slots in use.
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_qf_decode_emit(const T *filter, const uint32_t *occ, const uint32_t *cont, const uint32_t *sh, uint32_t q, uint32_t nwords,
+                                                           uint32_t valid, const long long *counts, const uint32_t *marks, uint32_t *out, uint64_t out_cap)
+{
+    const long long *runs = counts, *occs = counts + nwords, *used = counts + 2ull * nwords;
+    const uint64_t size = 1ull << q, stride = (uint64_t)gridDim.x * kBlock;
+    const long long nruns = runs[nwords - 1];
+    if (!nruns || marks[0] >= size) return;  // (an anchor exists in every quotient filter's table: see the file comment; none = not one, nothing to list)
+    const uint32_t x = marks[0], xw = x >> 5, xb = x & 31u;
+    const long long wrapped = excl(runs, xw) + __popc(~cont[xw] & (occ[xw] | sh[xw]) & below(xb)) - excl(occs, xw) - __popc(occ[xw] & below(xb));
+    for (uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x; p < size; p += stride) {
+        const uint32_t w = (uint32_t)(p >> 5), b = (uint32_t)p & 31u;
+        const uint32_t o = occ[w] & valid, c = cont[w] & valid, s = sh[w] & valid, inuse = o | c | s;
+        if (!((inuse >> b) & 1u)) continue;
+        const long long k = excl(runs, w) + __popc(~c & (o | s) & (0xFFFFFFFFu >> (31u - b))) - 1;  // this slot's run, in slot order (-1: the run wrapped in from the end)
+        long long idx = (k - wrapped) % nruns;
+        if (idx < 0) idx += nruns;
+        // the idx-th occupied quotient: the first word whose inclusive count passes idx, then the bit inside it
+        uint32_t lo = 0, hi = nwords - 1;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (occs[mid] > idx) hi = mid;
+            else lo = mid + 1;
+        }
+        uint32_t bits = occ[lo] & valid;
+        for (long long t = idx - excl(occs, lo); t > 0 && bits; --t) bits &= bits - 1u;
+        const uint32_t quot = (lo << 5) + (bits ? (uint32_t)__ffs(bits) - 1u : 0u);
+        const uint64_t at = (uint64_t)excl(used, w) + __popc(inuse & below(b));
+        if (at < out_cap) out[at] = (quot << (32u - q)) | (uint32_t)filter[p];
+    }
+}
+
+unsigned grid_of(uint64_t n)
+{
+    const uint64_t g = (n + kBlock - 1) / kBlock;
+    return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+}
+
+int check_q(uint32_t q)
+{
+    if (q < 3 || q > 31) return fail(PSK_EINVAL, "quotient must be between 3 and 31; %u was provided", q);
+    return PSK_OK;
+}
+
+uint32_t words_of(uint32_t q) { return q >= 5 ? 1u << (q - 5) : 1u; }
+uint32_t valid_of(uint32_t q) { return q >= 5 ? 0xFFFFFFFFu : (1u << (1u << q)) - 1u; }
+size_t rem_bytes(uint32_t q) { return 32 - q <= 8 ? 1 : (32 - q <= 16 ? 2 : 4); }
+
+}  // namespace
+
+extern "C" int psk_qf_build(uint32_t q, const uint32_t *sorted_hashes_dev, uint64_t n, void *filter_dev, uint32_t *occupied_dev, uint32_t *continuation_dev,
+                            uint32_t *shifted_dev, int32_t *scratch_dev, int device, void *stream)
+{
+    PSK_TRY(check_q(q));
+    if (!filter_dev || !occupied_dev || !continuation_dev || !shifted_dev) return fail(PSK_EINVAL, "NULL table pointer");
+    if (n > (1ull << q)) return fail(PSK_EINVAL, "%llu distinct hashes do not fit a table of 2^%u slots", (unsigned long long)n, q);
+    if (n && (!sorted_hashes_dev || !scratch_dev)) return fail(PSK_EINVAL, "NULL argument");
+    PSK_USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t wbytes = (size_t)words_of(q) * 4;
+    HIP_TRY(hipMemsetAsync(filter_dev, 0, rem_bytes(q) << q, st));
+    HIP_TRY(hipMemsetAsync(occupied_dev, 0, wbytes, st));
+    HIP_TRY(hipMemsetAsync(continuation_dev, 0, wbytes, st));
+    HIP_TRY(hipMemsetAsync(shifted_dev, 0, wbytes, st));
+    if (!n) return PSK_OK;
+    const uint32_t ntiles = (uint32_t)((n + kTile - 1) / kTile), rbits = 32 - q;
+    hipLaunchKernelGGL(k_qf_tile_max, dim3(ntiles), dim3(kBlock), 0, st, sorted_hashes_dev, n, rbits, scratch_dev);
+    hipLaunchKernelGGL(k_qf_tile_scan, dim3(1), dim3(kBlock), 0, st, scratch_dev, ntiles);
+    const int32_t *carry = scratch_dev;
+    if (rbits <= 8)
+        hipLaunchKernelGGL((k_qf_place<uint8_t>), dim3(ntiles), dim3(kBlock), 0, st, sorted_hashes_dev, n, q, carry, ntiles, (uint8_t *)filter_dev, occupied_dev, continuation_dev, shifted_dev);
+    else if (rbits <= 16)
+        hipLaunchKernelGGL((k_qf_place<uint16_t>), dim3(ntiles), dim3(kBlock), 0, st, sorted_hashes_dev, n, q, carry, ntiles, (uint16_t *)filter_dev, occupied_dev, continuation_dev, shifted_dev);
+    else
+        hipLaunchKernelGGL((k_qf_place<uint32_t>), dim3(ntiles), dim3(kBlock), 0, st, sorted_hashes_dev, n, q, carry, ntiles, (uint32_t *)filter_dev, occupied_dev, continuation_dev, shifted_dev);
+    HIP_TRY(hipGetLastError());
+    return PSK_OK;
+}
+
+extern "C" int psk_qf_check_alt(uint32_t q, const void *filter_dev, const uint32_t *occupied_dev, const uint32_t *continuation_dev, const uint32_t *shifted_dev,
+                                const uint32_t *hashes_dev, uint64_t n, uint8_t *out_dev, int device, void *stream)
+{
+    PSK_TRY(check_q(q));
+    if (!filter_dev || !occupied_dev || !continuation_dev || !shifted_dev) return fail(PSK_EINVAL, "NULL table pointer");
+    if (n && (!hashes_dev || !out_dev)) return fail(PSK_EINVAL, "NULL argument");
+    PSK_USE_DEVICE(device);
+    if (!n) return PSK_OK;
+    const psk::QfTable t{filter_dev, occupied_dev, continuation_dev, shifted_dev, q};
+    hipLaunchKernelGGL(k_qf_check_alt, dim3(grid_for_keys(n)), dim3(kBlock), 0, (hipStream_t)stream, t, hashes_dev, n, out_dev);
+    HIP_TRY(hipGetLastError());
+    return PSK_OK;
+}
+
+extern "C" int psk_qf_decode(uint32_t q, const void *filter_dev, const uint32_t *occupied_dev, const uint32_t *continuation_dev, const uint32_t *shifted_dev,
+                             int64_t *word_counts_dev, uint32_t *marks_dev, uint32_t *out_dev, uint64_t out_cap, int device, void *stream)
+{
+    PSK_TRY(check_q(q));
+    if (!filter_dev || !occupied_dev || !continuation_dev || !shifted_dev || !word_counts_dev || !marks_dev) return fail(PSK_EINVAL, "NULL argument");
+    PSK_USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t nwords = words_of(q), valid = valid_of(q);
+    if (!out_dev) {  // pass 1: the per-word counts and the two marks
+        HIP_TRY(hipMemsetAsync(marks_dev, 0xFF, 8, st));
+        hipLaunchKernelGGL(k_qf_decode_count, dim3(grid_of(nwords)), dim3(kBlock), 0, st, occupied_dev, continuation_dev, shifted_dev, nwords, valid,
+                           (long long *)word_counts_dev, marks_dev);
+        HIP_TRY(hipGetLastError());
+        return PSK_OK;
+    }
+    const long long *counts = (const long long *)word_counts_dev;
+    const unsigned grid = grid_of(1ull << q);
+    const uint32_t rbits = 32 - q;
+    if (rbits <= 8)
+        hipLaunchKernelGGL((k_qf_decode_emit<uint8_t>), dim3(grid), dim3(kBlock), 0, st, (const uint8_t *)filter_dev, occupied_dev, continuation_dev, shifted_dev, q, nwords, valid, counts, marks_dev, out_dev, out_cap);
+    else if (rbits <= 16)
+        hipLaunchKernelGGL((k_qf_decode_emit<uint16_t>), dim3(grid), dim3(kBlock), 0, st, (const uint16_t *)filter_dev, occupied_dev, continuation_dev, shifted_dev, q, nwords, valid, counts, marks_dev, out_dev, out_cap);
+    else
+        hipLaunchKernelGGL((k_qf_decode_emit<uint32_t>), dim3(grid), dim3(kBlock), 0, st, (const uint32_t *)filter_dev, occupied_dev, continuation_dev, shifted_dev, q, nwords, valid, counts, marks_dev, out_dev, out_cap);
+    HIP_TRY(hipGetLastError());
+    return PSK_OK;
+}

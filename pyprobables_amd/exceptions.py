@@ -36,6 +36,10 @@ class CountMinSketchError(ProbablesBaseException):
     """mismatched count-min sketches in ``join``"""
 
 
+class QuotientFilterError(ProbablesBaseException):
+    """a QuotientFilter that cannot be built, grown, shrunk or merged (reference exceptions.py QuotientFilterError)"""
+
+
 class NativeLibraryError(RuntimeError):
     """libpsk_hip.so (the HIP engine) is missing, failed to load, or reported an error.
 
