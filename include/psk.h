@@ -133,7 +133,9 @@ int psk_set_option(const char *name, int64_t value);
 int psk_get_option(const char *name, int64_t *value);
 /* Per-sketch options (round 4): "partition_min_keys", "cbf_lookup_shadow", "auto_combine", "update_window", "update_window_keys",
  * "scratch_budget_bytes", "remove_exact", "bloom_lookup" can differ between the sketches of one process -- psk_set_option keeps the
- * DEFAULT of each, psk_sketch_set_option overrides it for one handle (value INT64_MIN: follow the default again).  One more name exists
+ * DEFAULT of each, psk_sketch_set_option overrides it for one handle (value INT64_MIN: follow the default again).  A call on a handle
+ * works under the handle's overrides and, for the rest, the defaults as they stand when the call enters: a default another thread changes
+ * meanwhile holds from the handle's next call on.  One more name exists
  * per sketch only: "table_private" = 1 declares that whoever holds the pointer of a caller-owned table (ext_table) announces EVERY write it
  * makes behind the engine's back (psk_table_info before, psk_rescan_bound after); without that promise -- and between psk_table_info(&ptr)
  * and the next psk_rescan_bound -- the engine keeps nothing derived from the table (the 4-bit images of repeated psk_cbf_check calls).

@@ -149,14 +149,141 @@ static int for_each_scratch(psk_sketch *s, F &&f)
     return PSK_OK;
 }
 
-static inline void ho_apply(const psk_sketch *s);  // (the handle's option overrides -> this thread's effective values; defined with the options below)
+// ------------------------------------------------------------------ options
+// Every process-wide option variable, defined ONCE (declared in psk_host.hpp), directly above the table that names it.
+int64_t g_part_mode = 1;                   // 0 = direct kernels only, 1 = large batches take the partitioned passes
+int64_t g_part_max_keys = 1 << 26;         // keys per partition round (bounds the bucket buffer: ~2 GB of scratch at k = 7)
+int64_t g_part_cache_bytes = 240 << 20;    // bucket-buffer budget per round: the part of the 256 MB MALL we count on (part_round_keys)
+int64_t g_part_two_level_slices = 2048;    // tables cut into more slices than this take the two-level path (0 = never)
+int64_t g_part_debug = 0;                  // ablation bits for bench runs (PartGeom::dbg); 0 in production
+int64_t g_part_tile_threads = 0;           // pass 1 workgroup shape for k <= 8: 0 = auto (launch_scatter), 512 / 1024 = forced
+int64_t g_part_even_tiles = 1;             // pass 1 evens the tile size out over the workgroups
+int64_t g_part_dense_groups = 40;          // pass 2 walks a wave's segments end to end below this many groups per segment (for_each_batch_at); 0 = never
+int64_t g_part_bins = 1;                   // pass 1 through fixed-capacity bins wherever eligible (psk_part_bins.hpp); 0 = k_part_scatter everywhere
+int64_t g_ragged_sort = 1;                 // pass 1 hands ragged keys to its lanes in order of length (psk_partition.hpp sort_tile); 0 = batch order
+int64_t g_lookup_half = 1;                 // counter lookups into 2^26 .. 2^27 counters: 2^16-counter slices of 16-bit values
+int64_t g_lookup_nibble = 1;               // CBF lookups into big tables: 4-bit slice images (psk_nibble.hpp) from cells / 16 probes on; 2 = always, 0 = never
+int64_t g_update_nibble = 1;               // CBF unit adds / decrements into big tables: 4-bit delta images, one level; 0 = the two-level 32-bit path
+int64_t g_nib_min_lg_lookup = 23;          // least log2(counters) of the 4-bit lookups (nib_geometry; crossovers: scripts/ab_nib_threshold.py)
+int64_t g_nib_min_lg_update = 24;          // ... and the table must exceed 2^this for the 4-bit updates
+int64_t g_small_weights = 1;               // weighted CMS adds in the compact probe format: 0 never, 1 by the hint (psk_sketch::wt), 2 always (tests)
+int64_t g_remove_dryrun = 1;               // validated unit CBF removes into big tables: optimistic decrement first (psk_nibble.hpp)
+int64_t g_combine_keys = 1 << 26;          // keys per list of psk_cbf_update_combined: 1 GiB of 16-byte keys per list
+int64_t g_auto_combine_keys = 1 << 24;     // keys per list of "auto_combine" (~0.8 GB of segments for k = 7, allocated on first use)
+int64_t g_window_wide = 1;                 // update windows on tables of few slices: five probe groups per lane and phase, byte-wide counts (0: three, nibbles)
+int64_t g_window_tile = 0;                 // keys per pass-1 tile of an update window: 0 = by the rule in window_scatter, 2048 / 4096 = forced
+int64_t g_window_force_fail = 0;           // tests: pretend a window's proof failed (exercises undo + replay on a well-formed stream)
+int64_t g_merge_single_rank = 0;           // 1: psk_merge_* run the collective path even with one rank (tests)
+int64_t g_lazy_clear = 1;                  // psk_clear of a Bloom table the engine alone reads is deferred; 0 = sweep at once
+int64_t g_host_poll_us = 200;              // how long a tiny PSK_HOST call polls its mailbox before it waits for the stream; 0 = never poll
+// read-only counters (tests, bench): calls / batches that took the path named
+int64_t g_cbf_ordered_replays = 0;         // remove batches whose result depended on the order inside them: undone, replayed in order
+int64_t g_window_folds = 0;                // update windows applied by the fold
+int64_t g_window_replays = 0;              // ... and replayed batch by batch
+int64_t g_small_weights_used = 0;          // weighted CMS adds that travelled in the compact format
+int64_t g_cbf_shadow_hits = 0;             // nibble-slice lookups that loaded kept images (psk_sketch::shadow)
+int64_t g_running_fast = 0;                // psk_cms_add_running calls that took the parallel passes
+int64_t g_running_sequential = 0;          // ... and the one-lane kernel
+// Process DEFAULTS of the per-sketch options, in HandleOpt order.  Nothing but the option calls and resolve_options touches them: the engine
+// reads psk_sketch::eff.
+static int64_t g_sketch_default[HO_COUNT] = {
+    1 << 16,  // partition_min_keys: least batch for the partitioned passes -- x1 for Bloom inserts, x4 for lookups / counter adds (part_wanted)
+    1,        // cbf_lookup_shadow: nibble-slice lookups keep their 4-bit images while the table is unchanged (psk_sketch::shadow; cells / 2 bytes)
+    1,        // auto_combine: small unit-weight add batches into big tables wait as scattered probes (adds commute: exact)
+    1,        // update_window: small unit add / remove batches into big tables share one proven pass (psk_window.hpp)
+    1 << 27,  // update_window_keys: most keys a window holds (16 bytes each); also capped by cells / 2 and the scratch budget
+    0,        // scratch_budget_bytes: cap on a handle's partition scratch (more, smaller rounds); 0 = none
+    1,        // remove_exact: order-dependent remove batches are replayed in order; 0 = clamped and tallied as violations
+    2,        // bloom_lookup: 0 keyed probes + miss stores, 1 return trip, 3 tile flags, 4 lazy gathers, 2 = by the observed miss rate
+};
+
+// ONE table for every option.  Classes (include/psk.h lists the first by name):
+//   supported   tunables of the shipped library a caller may have a reason to touch;
+//   threshold   where the engine switches between its kernel families, and test hooks -- tests steer small inputs onto the big-table paths with them;
+//   knob        "part_debug" alone, the ablation / phase-profile bits of the measuring tools: compiled in only with -DPSK_BENCH_KNOBS=1
+//               (python -m pyprobables_amd.build --knobs -> libpsk_hip_knobs.so), the shipped library answers "unknown option";
+//   read-only   counters tests read back.
+// Per-sketch options (ho >= 0): the row points at the process default; the handle holds the override (psk_sketch::opt), and every entry
+// point that takes a handle resolves the two into psk_sketch::eff on entry (resolve_options).
+namespace {
+enum OptClass { kOptSupported, kOptThreshold, kOptKnob, kOptReadOnly };
+struct OptDesc {
+    const char *name;
+    int64_t *var;
+    OptClass cls;
+    int64_t lo;   // smallest value accepted (smaller ones are raised to it)
+    int ho = -1;  // HandleOpt of a per-sketch option; -1: process-wide
+};
+constexpr int64_t kAny = INT64_MIN;
+const OptDesc kOptions[] = {
+    // supported, per sketch
+    {"partition_min_keys", &g_sketch_default[HO_PART_MIN_KEYS], kOptSupported, 1, HO_PART_MIN_KEYS},
+    {"cbf_lookup_shadow", &g_sketch_default[HO_CBF_SHADOW], kOptSupported, kAny, HO_CBF_SHADOW},
+    {"auto_combine", &g_sketch_default[HO_AUTO_COMBINE], kOptSupported, kAny, HO_AUTO_COMBINE},
+    {"update_window", &g_sketch_default[HO_WINDOW], kOptSupported, kAny, HO_WINDOW},
+    {"update_window_keys", &g_sketch_default[HO_WINDOW_KEYS], kOptSupported, kAny, HO_WINDOW_KEYS},
+    {"scratch_budget_bytes", &g_sketch_default[HO_SCRATCH_BUDGET], kOptSupported, kAny, HO_SCRATCH_BUDGET},
+    {"remove_exact", &g_sketch_default[HO_REMOVE_EXACT], kOptSupported, kAny, HO_REMOVE_EXACT},
+    {"bloom_lookup", &g_sketch_default[HO_BLOOM_LOOKUP], kOptSupported, kAny, HO_BLOOM_LOOKUP},
+    // supported, process-wide
+    {"partition", &g_part_mode, kOptSupported, kAny},
+    {"partition_max_keys", &g_part_max_keys, kOptSupported, 1024},
+    {"partition_cache_bytes", &g_part_cache_bytes, kOptSupported, kAny},
+    {"combine_keys", &g_combine_keys, kOptSupported, kAny},
+    {"cms_small_weights", &g_small_weights, kOptSupported, kAny},
+    {"pass1_bins", &g_part_bins, kOptSupported, kAny},
+    {"merge_single_rank", &g_merge_single_rank, kOptSupported, kAny},
+    {"lazy_clear", &g_lazy_clear, kOptSupported, kAny},
+    // thresholds of the path choice, test hooks
+    {"partition_two_level_slices", &g_part_two_level_slices, kOptThreshold, kAny},
+    {"auto_combine_keys", &g_auto_combine_keys, kOptThreshold, kAny},
+    {"tile_threads", &g_part_tile_threads, kOptThreshold, kAny},
+    {"even_tiles", &g_part_even_tiles, kOptThreshold, kAny},
+    {"dense_walk_groups", &g_part_dense_groups, kOptThreshold, kAny},
+    {"lookup_half_slices", &g_lookup_half, kOptThreshold, kAny},
+    {"remove_optimistic", &g_remove_dryrun, kOptThreshold, kAny},
+    {"lookup_nibble_slices", &g_lookup_nibble, kOptThreshold, kAny},
+    {"update_nibble_slices", &g_update_nibble, kOptThreshold, kAny},
+    {"nibble_min_lg_lookup", &g_nib_min_lg_lookup, kOptThreshold, 20},
+    {"nibble_min_lg_update", &g_nib_min_lg_update, kOptThreshold, 20},
+    {"update_window_tile", &g_window_tile, kOptThreshold, kAny},
+    {"update_window_wide", &g_window_wide, kOptThreshold, kAny},
+    {"update_window_force_fail", &g_window_force_fail, kOptThreshold, kAny},
+    {"ragged_sort", &g_ragged_sort, kOptThreshold, kAny},
+    {"host_poll_us", &g_host_poll_us, kOptThreshold, kAny},
+    // read-only counters
+    {"cbf_ordered_replays", &g_cbf_ordered_replays, kOptReadOnly, kAny},
+    {"update_window_folds", &g_window_folds, kOptReadOnly, kAny},
+    {"update_window_replays", &g_window_replays, kOptReadOnly, kAny},
+    {"cms_small_weights_used", &g_small_weights_used, kOptReadOnly, kAny},
+    {"cbf_lookup_shadow_hits", &g_cbf_shadow_hits, kOptReadOnly, kAny},
+    {"cms_running_fast", &g_running_fast, kOptReadOnly, kAny},
+    {"cms_running_sequential", &g_running_sequential, kOptReadOnly, kAny},
+    // measuring tools (bench builds only)
+    {"part_debug", &g_part_debug, kOptKnob, kAny},
+};
+const OptDesc *opt_find(const char *name)
+{
+    for (const OptDesc &d : kOptions)
+        if (!strcmp(name, d.name)) return (d.cls == kOptKnob && !kBenchKnobs) ? nullptr : &d;
+    return nullptr;
+}
+}  // namespace
+
+// The options in force for the call that enters now: the handle's override, else the process default of this moment (another thread may
+// change a default at any time; it never takes effect in the middle of a call, which asks the same question more than once).
+void resolve_options(psk_sketch *s)
+{
+    for (int i = 0; i < HO_COUNT; ++i) s->eff[i] = s->opt[i] != kHoUnset ? s->opt[i] : __atomic_load_n(&g_sketch_default[i], __ATOMIC_RELAXED);
+}
+
 extern "C" int psk_destroy(psk_sketch *s)
 {
     if (!s) return PSK_OK;
     DeviceScope scope;
     (void)scope.enter(s->device);
     if (!s->owns_table && s->table) {  // the caller's table outlives the handle: write-combined updates still waiting must reach it
-        ho_apply(s);  // (under THIS sketch's options, not those of whatever handle the thread used last: remove_exact, update_window ...)
+        resolve_options(s);  // (psk_destroy accepts NULL, so it does not pass the handle gate)
         if (flush_combined(s, nullptr) == PSK_OK) (void)hipStreamSynchronize(nullptr);
     }
     if (s->owns_table && s->table) hipFree(s->table);
@@ -175,48 +302,6 @@ extern "C" int psk_destroy(psk_sketch *s)
     delete s;
     return PSK_OK;
 }
-
-// ---- per-sketch options (psk_host.hpp HandleOpt): process defaults, names, and the refresh every handle entry point does
-static const char *const kHoNames[HO_COUNT] = {"partition_min_keys", "cbf_lookup_shadow", "auto_combine", "update_window", "update_window_keys",
-                                                "scratch_budget_bytes", "remove_exact", "bloom_lookup"};
-static int64_t d_opt[HO_COUNT] = {1 << 16, 1, 1, 1, 1 << 27, 0, 1, 2};  // (== the thread-local variables' initial values)
-static int64_t *ho_var(int i)
-{
-    switch (i) {
-        case HO_PART_MIN_KEYS: return &g_part_min_keys;
-        case HO_CBF_SHADOW: return &g_cbf_shadow;
-        case HO_AUTO_COMBINE: return &g_auto_combine;
-        case HO_WINDOW: return &g_window;
-        case HO_WINDOW_KEYS: return &g_window_keys;
-        case HO_SCRATCH_BUDGET: return &g_scratch_budget;
-        case HO_REMOVE_EXACT: return &g_remove_exact;
-        default: return &g_bloom_lookup;
-    }
-}
-static int ho_index(const char *name)
-{
-    for (int i = 0; i < HO_COUNT; ++i)
-        if (!strcmp(name, kHoNames[i])) return i;
-    return -1;
-}
-static inline void ho_apply(const psk_sketch *s)
-{
-    for (int i = 0; i < HO_COUNT; ++i) *ho_var(i) = (s && s->opt[i] != kHoUnset) ? s->opt[i] : __atomic_load_n(&d_opt[i], __ATOMIC_RELAXED);
-}
-
-#define CHECK_HANDLE_RO(s, want_kind)                                                    \
-    do {                                                                                 \
-        if (!(s)) return fail(PSK_EINVAL, "sketch handle is NULL");                      \
-        if ((want_kind) >= 0 && (s)->kind != (want_kind))                                \
-            return fail(PSK_EINVAL, "wrong sketch kind %d for this call", (s)->kind);    \
-        ho_apply(s);                                                                     \
-    } while (0);                                                                         \
-    PSK_USE_DEVICE((s)->device)
-// every entry point that may change the table (or hands its pointer out) moves the table's version on: what was derived from the
-// table -- psk_sketch::shadow, the 4-bit images of the nibble-slice lookup -- is stale from here on.  Read-only entries: _RO.
-#define CHECK_HANDLE(s, want_kind)                                                       \
-    CHECK_HANDLE_RO(s, want_kind);                                                       \
-    ++(s)->table_version
 
 // table (padded to 16 bytes) and the handle's counter block, zeroed by one kernel
 // (round 4: nontemporal stores measured SLOWER for this write-only sweep -- 247 vs 215 us for the 1 GiB table of cfg 4 -- unlike the
@@ -249,8 +334,6 @@ static int drop_pending(psk_sketch *s, hipStream_t st)
     s->win.batches.clear();
     return scat_drop(s, st);
 }
-
-int64_t g_lazy_clear = 1;  // psk_set_option("lazy_clear", 0): every psk_clear sweeps the table at once (A/B of the deferred clear)
 
 // one launch for the table AND the counter block (two fills are two ~5 us launches; clear sits in every bench step)
 static int launch_clear(psk_sketch *s, hipStream_t st)
@@ -398,7 +481,6 @@ int raise_dyn_lds(const void *kernel, size_t bytes)
 // ends when its answer is in host memory; the stream wait (a barrier packet, its signal, the runtime's bookkeeping: ~5 us of a ~15 us
 // call) is what the reference's per-key callers would otherwise pay on every `key in blm`.  The poll gives up after host_poll_us
 // microseconds (option; 0 = never poll) and falls back to the stream wait, which also reports a kernel that died.
-int64_t g_host_poll_us = 200;
 struct Mailbox {
     volatile uint32_t *word = nullptr;  // nullptr: not armed -- finish() waits for the stream
     uint32_t seq = 0;
@@ -635,109 +717,13 @@ static int direct_apply(psk_sketch *s, const Batch &b, const void *data, int whe
     return finish(where, o, st, &mb);
 }
 
-// ------------------------------------------------- partitioned (large-batch) path: options
-int64_t g_part_mode = 1;
-__thread int64_t g_part_min_keys = 1 << 16;   // x1 for Bloom inserts, x4 for lookups / counter adds (part_wanted)
-int64_t g_part_max_keys = 1 << 26;   // keys per partition round (bounds the bucket buffer: ~2 GB of scratch at k = 7; sized for 288 GB of HBM --
-                                     // every round into a big table ends in a pass over the whole table, so fewer, larger rounds)
-int64_t g_part_cache_bytes = 240 << 20;  // bucket-buffer budget per round: the part of the 256 MB MALL we count on
-int64_t g_part_two_level_slices = 2048;     // tables cut into more slices than this take the two-level path (0 = never)
-int64_t g_part_debug = 0;            // ablation bits for bench runs (see PartGeom::dbg); 0 in production
-__thread int64_t g_bloom_lookup = 2;
-int64_t g_part_tile_threads = 0, g_part_even_tiles = 1;
-int64_t g_lookup_half = 1;
-int64_t g_remove_dryrun = 1;   // validated unit-weight CBF removes into big tables: optimistic decrement first (psk_nibble.hpp), option "remove_optimistic"
-__thread int64_t g_scratch_budget = 0;  // psk_set_option("scratch_budget_bytes"): cap on a handle's partition scratch (more, smaller rounds); 0 = none
-int64_t g_lookup_nibble = 1;   // CBF lookups into 2^25 .. 2^29 counters: 4-bit slice images (psk_nibble.hpp) from cells / 16 probes on; 2 = always; 0 = the 32-bit / 16-bit slices or direct
-int64_t g_small_weights_used = 0;
-int64_t g_small_weights = 1;   // PayWeightSmall for weighted CountMinSketch adds (psk_sketch::wt)
-int64_t g_cbf_shadow_hits = 0;
-int64_t g_running_fast = 0, g_running_sequential = 0;   // psk_cms_add_running calls that took the parallel passes / the one-lane kernel (read-only options)
-__thread int64_t g_cbf_shadow = 1;  // nibble-slice lookups keep their 4-bit images while the table is unchanged (psk_sketch::shadow; cells / 2 bytes)
-int64_t g_nib_min_lg_lookup = 23, g_nib_min_lg_update = 24;  // see nib_geometry (psk_host.hpp); measured crossovers: scripts/ab_nib_threshold.py
-int64_t g_ragged_sort = 1;    // pass 1's per-tile length sort of ragged keys (A/B: 0 = batch order); option "ragged_sort"
-int64_t g_window_wide = 1;    // update windows on tables of few slices: the fold with five probe groups per lane and phase and byte-wide group counts (0: three, nibbles)
-int64_t g_window_tile = 0;    // keys per pass-1 tile of an update window: 0 = rule (4096 for tables of many slices), 2048 / 4096 forced; option "update_window_tile"
-int64_t g_update_nibble = 1;   // CBF unit-weight adds / decrements into 2^26 .. 2^29 counters: 4-bit delta images, one level; 0 = two-level 32-bit path
-int64_t g_part_bins = 1;   // pass 1 through fixed-capacity bins wherever eligible (psk_part_bins.hpp); option "pass1_bins"
-int64_t g_part_dense_groups = 40;   // pass 2: segments of fewer groups (mean) are walked end to end (for_each_batch_at); 0 = never
-extern PSK_HIDDEN int64_t g_merge_single_rank;  // psk_merge.hip
-
-// ---- process-wide options: ONE table.  Three classes (include/psk.h lists the first by name):
-//   supported   tunables of the shipped library a caller may have a reason to touch;
-//   threshold   where the engine switches between its kernel families, and test hooks -- tests steer small inputs onto the big-table paths with them;
-//   knob        "part_debug" alone, the ablation / phase-profile bits of the measuring tools: compiled in only with -DPSK_BENCH_KNOBS=1
-//               (python -m pyprobables_amd.build --knobs -> libpsk_hip_knobs.so), the shipped library answers "unknown option";
-//   read-only   counters tests read back.
-// (the per-sketch options -- kHoNames -- are handled in front of the table: their process defaults live in d_opt)
-namespace {
-enum OptClass { kOptSupported, kOptThreshold, kOptKnob, kOptReadOnly };
-struct OptDesc {
-    const char *name;
-    int64_t *var;
-    OptClass cls;
-    int64_t lo;  // smallest value accepted (smaller ones are raised to it)
-};
-constexpr int64_t kAny = INT64_MIN;
-const OptDesc kOptions[] = {
-    // supported
-    {"partition", &g_part_mode, kOptSupported, kAny},
-    {"partition_max_keys", &g_part_max_keys, kOptSupported, 1024},
-    {"partition_cache_bytes", &g_part_cache_bytes, kOptSupported, kAny},
-    {"combine_keys", &g_combine_keys, kOptSupported, kAny},
-    {"cms_small_weights", &g_small_weights, kOptSupported, kAny},
-    {"pass1_bins", &g_part_bins, kOptSupported, kAny},
-    {"merge_single_rank", &g_merge_single_rank, kOptSupported, kAny},
-    {"lazy_clear", &g_lazy_clear, kOptSupported, kAny},
-    // thresholds of the path choice, test hooks
-    {"partition_two_level_slices", &g_part_two_level_slices, kOptThreshold, kAny},
-    {"auto_combine_keys", &g_auto_combine_keys, kOptThreshold, kAny},
-    {"tile_threads", &g_part_tile_threads, kOptThreshold, kAny},
-    {"even_tiles", &g_part_even_tiles, kOptThreshold, kAny},
-    {"dense_walk_groups", &g_part_dense_groups, kOptThreshold, kAny},
-    {"lookup_half_slices", &g_lookup_half, kOptThreshold, kAny},
-    {"remove_optimistic", &g_remove_dryrun, kOptThreshold, kAny},
-    {"lookup_nibble_slices", &g_lookup_nibble, kOptThreshold, kAny},
-    {"update_nibble_slices", &g_update_nibble, kOptThreshold, kAny},
-    {"nibble_min_lg_lookup", &g_nib_min_lg_lookup, kOptThreshold, 20},
-    {"nibble_min_lg_update", &g_nib_min_lg_update, kOptThreshold, 20},
-    {"update_window_tile", &g_window_tile, kOptThreshold, kAny},
-    {"update_window_wide", &g_window_wide, kOptThreshold, kAny},
-    {"update_window_force_fail", &g_window_force_fail, kOptThreshold, kAny},
-    {"ragged_sort", &g_ragged_sort, kOptThreshold, kAny},
-    {"host_poll_us", &g_host_poll_us, kOptThreshold, kAny},
-    // read-only counters
-    {"cbf_ordered_replays", &g_cbf_ordered_replays, kOptReadOnly, kAny},
-    {"update_window_folds", &g_window_folds, kOptReadOnly, kAny},
-    {"update_window_replays", &g_window_replays, kOptReadOnly, kAny},
-    {"cms_small_weights_used", &g_small_weights_used, kOptReadOnly, kAny},
-    {"cbf_lookup_shadow_hits", &g_cbf_shadow_hits, kOptReadOnly, kAny},
-    {"cms_running_fast", &g_running_fast, kOptReadOnly, kAny},
-    {"cms_running_sequential", &g_running_sequential, kOptReadOnly, kAny},
-    // measuring tools (bench builds only)
-    {"part_debug", &g_part_debug, kOptKnob, kAny},
-};
-const OptDesc *opt_find(const char *name)
-{
-    for (const OptDesc &d : kOptions)
-        if (!strcmp(name, d.name)) return (d.cls == kOptKnob && !kBenchKnobs) ? nullptr : &d;
-    return nullptr;
-}
-}  // namespace
-
 extern "C" int psk_set_option(const char *name, int64_t value)
 {
     if (!name) return fail(PSK_EINVAL, "option name is NULL");
-    if (const int i = ho_index(name); i >= 0) {  // a default of the per-sketch options (sketches without an override follow it)
-        if (i == HO_PART_MIN_KEYS && value < 1) value = 1;
-        __atomic_store_n(&d_opt[i], value, __ATOMIC_RELAXED);
-        *ho_var(i) = value;
-        return PSK_OK;
-    }
     const OptDesc *d = opt_find(name);
     if (!d || d->cls == kOptReadOnly) return fail(PSK_EINVAL, d ? "option %s is read-only" : "unknown option %s", name);
     if (value < d->lo) value = d->lo;
-    *d->var = value;
+    __atomic_store_n(d->var, value, __ATOMIC_RELAXED);  // (of a per-sketch option: the default; sketches without an override follow it from their next call on)
     return PSK_OK;
 }
 
@@ -767,10 +753,10 @@ extern "C" int psk_sketch_set_option(psk_sketch *s, const char *name, int64_t va
         ++s->table_version;
         return PSK_OK;
     }
-    const int i = ho_index(name);
-    if (i < 0) return fail(PSK_EINVAL, "%s is not a per-sketch option", name);
-    if (i == HO_PART_MIN_KEYS && value != kHoUnset && value < 1) value = 1;
-    s->opt[i] = value;  // (kHoUnset = INT64_MIN: follow the process default again)
+    const OptDesc *d = opt_find(name);
+    if (!d || d->ho < 0) return fail(PSK_EINVAL, "%s is not a per-sketch option", name);
+    if (value != kHoUnset && value < d->lo) value = d->lo;
+    s->opt[d->ho] = value;  // (kHoUnset = INT64_MIN: follow the process default again)
     return PSK_OK;
 }
 
@@ -785,22 +771,18 @@ extern "C" int psk_sketch_get_option(psk_sketch *s, const char *name, int64_t *v
         *value = s->win.n ? (int64_t)s->win.batches.size() : 0;
         return PSK_OK;
     }
-    const int i = ho_index(name);
-    if (i < 0) return fail(PSK_EINVAL, "%s is not a per-sketch option", name);
-    *value = s->opt[i] != kHoUnset ? s->opt[i] : __atomic_load_n(&d_opt[i], __ATOMIC_RELAXED);
+    const OptDesc *d = opt_find(name);
+    if (!d || d->ho < 0) return fail(PSK_EINVAL, "%s is not a per-sketch option", name);
+    *value = s->opt[d->ho] != kHoUnset ? s->opt[d->ho] : __atomic_load_n(d->var, __ATOMIC_RELAXED);
     return PSK_OK;
 }
 
 extern "C" int psk_get_option(const char *name, int64_t *value)
 {
     if (!name || !value) return fail(PSK_EINVAL, "NULL argument");
-    if (const int i = ho_index(name); i >= 0) {
-        *value = __atomic_load_n(&d_opt[i], __ATOMIC_RELAXED);
-        return PSK_OK;
-    }
     const OptDesc *d = opt_find(name);
     if (!d) return fail(PSK_EINVAL, "unknown option %s", name);
-    *value = *d->var;
+    *value = __atomic_load_n(d->var, __ATOMIC_RELAXED);
     return PSK_OK;
 }
 
@@ -946,7 +928,7 @@ extern "C" int psk_bloom_check_bits(psk_sketch *s, int layout, const void *data,
     OutBuf o;
     PSK_TRY(stage_out(s->s_out, out_bits, nwords * 8, where, &o));
     unsigned long long *hits_dev = (unsigned long long *)hits;
-    const bool big = n && !s->pend.active && part_wanted(n, s->k, 4);
+    const bool big = n && !s->pend.active && part_wanted(s, n, s->k, 4);
     if (where == PSK_HOST || big) PSK_TRY(ensure(s->s_aux, 16 + (big ? n : 0)));  // hits (staged for host callers) | a byte per key
     if (where == PSK_HOST) {
         hits_dev = (unsigned long long *)s->s_aux.p;
@@ -1019,8 +1001,6 @@ static int settle_acct(psk_sketch *s, const W *w_dev, uint64_t n, hipStream_t st
 }
 
 // ----------------------------------------------------- CountingBloomFilter
-int64_t g_combine_keys = 1 << 26;  // keys per write-combining list (psk_set_option "combine_keys"): 1 GiB of 16-byte keys per list
-
 // the direct kernels of an unordered CBF update (w = nullptr: unit weights)
 static int cbf_apply_direct(psk_sketch *s, const Batch &b, const uint32_t *w, bool remove, hipStream_t st)
 {
@@ -1046,9 +1026,6 @@ static int cbf_apply_device(psk_sketch *s, const Batch &b, const uint32_t *w, bo
 }
 
 // ---- write-combined updates as scattered probes (psk_sketch::scat, psk_nibble.hpp)
-__thread int64_t g_auto_combine = 1;            // psk_cbf_add: small unit-weight batches into big tables wait as scattered probes (adds commute: exact)
-int64_t g_auto_combine_keys = 1 << 24; // keys per list in that mode (~0.8 GB of segments for k = 7, allocated on first use)
-
 // a flush (or drop) on another stream than the last append must not overtake it
 // (the event is recorded only when a second stream shows up: one per append put a barrier packet -- ~5 us of dispatch bubble --
 // behind every 1 M-key batch of BASELINE cfg 4, 0.45 ms per step)
@@ -1136,7 +1113,7 @@ static int scat_append(psk_sketch *s, const Batch &b, uint64_t cap, hipStream_t 
     const PartGeom &g = s->scat.g;
     const uint64_t part_bytes = (uint64_t)g.nbuckets * g.nwg * g.segcap * 16 + 256, cnt_bytes = (uint64_t)g.nbuckets * g.nwg * 4 + 128;
     if (l.part.cap < part_bytes || l.cnt.cap < cnt_bytes) {  // first use (or released): allocate, counts start at zero
-        if (g_scratch_budget > 0 && (int64_t)(part_bytes + cnt_bytes) > g_scratch_budget) return PSK_OK;  // (not taken: the direct path serves)
+        if (s->eff[HO_SCRATCH_BUDGET] > 0 && (int64_t)(part_bytes + cnt_bytes) > s->eff[HO_SCRATCH_BUDGET]) return PSK_OK;  // (not taken: the direct path serves)
         if (ensure(l.part, part_bytes) != PSK_OK || ensure(l.cnt, cnt_bytes) != PSK_OK) return PSK_OK;    // out of memory costs the shortcut, not the add
         HIP_TRY(hipMemsetAsync(l.cnt.p, 0, cnt_bytes, st));
         l.n = 0;
@@ -1181,26 +1158,22 @@ static int borrowed_flush(psk_sketch *s, psk_sketch::BorrowList &bl, bool remove
 
 // ---- update windows (psk_window.hpp): small unit-weight add / remove batches of 16-byte keys into big tables wait, in arrival order,
 // as key copies; win_flush applies them in one pass over the table, proving the removes while it folds -- or replays them one by one
-__thread int64_t g_window = 1;                // option "update_window"
-__thread int64_t g_window_keys = 1 << 27;     // option "update_window_keys": most keys a window holds (16 bytes each); also cells / 2 and the scratch budget
-int64_t g_window_folds = 0, g_window_replays = 0;  // windows applied by the fold / replayed batch by batch (tests, bench)
-int64_t g_window_force_fail = 0;     // tests: pretend the proof failed (exercises undo + replay on a well-formed stream)
 constexpr size_t kWinMaxBatches = 4096;
 
 static uint64_t win_capacity(const psk_sketch *s)
 {
     uint64_t cap = s->m / 2;  // (BASELINE cfg 4's whole 74.5 M-operation step is one window of the 2^28-counter table)
     if (cap < (1u << 20)) cap = 1u << 20;
-    if (g_window_keys > 0 && cap > (uint64_t)g_window_keys) cap = (uint64_t)g_window_keys;
-    cap = cap_round_by_budget(cap, 16.0 + (double)s->k * (16.0 / 6.0) * 1.5);  // key copy + probe groups with their padding
+    if (s->eff[HO_WINDOW_KEYS] > 0 && cap > (uint64_t)s->eff[HO_WINDOW_KEYS]) cap = (uint64_t)s->eff[HO_WINDOW_KEYS];
+    cap = cap_round_by_budget(s, cap, 16.0 + (double)s->k * (16.0 / 6.0) * 1.5);  // key copy + probe groups with their padding
     return cap;
 }
 
 static bool win_eligible(const psk_sketch *s, int layout, const void *data, uint32_t key_len, const uint32_t *weights, uint64_t n)
 {
     PartGeom g;
-    return s->kind == PSK_KIND_CBF && g_window != 0 && g_update_nibble != 0 && !weights && layout == PSK_KEYS_FIXED && key_len == 16 && data && n != 0 &&
-           (int64_t)n >= g_part_min_keys && n * (uint64_t)s->k < s->m / 8 && s->k <= 32 && n <= win_capacity(s) && nib_geometry(s->m, true, &g);
+    return s->kind == PSK_KIND_CBF && s->eff[HO_WINDOW] != 0 && g_update_nibble != 0 && !weights && layout == PSK_KEYS_FIXED && key_len == 16 && data && n != 0 &&
+           (int64_t)n >= s->eff[HO_PART_MIN_KEYS] && n * (uint64_t)s->k < s->m / 8 && s->k <= 32 && n <= win_capacity(s) && nib_geometry(s->m, true, &g);
 }
 
 static int cbf_remove_device(psk_sketch *s, const Batch &b, const uint32_t *w, hipStream_t st);
@@ -1209,8 +1182,7 @@ static int cbf_remove_device(psk_sketch *s, const Batch &b, const uint32_t *w, h
 // rule the fold out, and the windows whose proof failed)
 static int win_replay(psk_sketch *s, const void *keys, const std::vector<psk_sketch::WinBatch> &batches, hipStream_t st)
 {
-    ++s->win.replays;
-    ++g_window_replays;
+    __atomic_add_fetch(&g_window_replays, 1, __ATOMIC_RELAXED);
     for (const auto &wb : batches) {
         const Batch b{PSK_KEYS_FIXED, wb.ext ? wb.ext : (const void *)((const uint8_t *)keys + wb.start * 16), nullptr, wb.n, 16};
         if (wb.remove) PSK_TRY(cbf_remove_device(s, b, nullptr, st));
@@ -1252,8 +1224,7 @@ static int win_flush(psk_sketch *s, hipStream_t st)
         bool launched = false, ok = false;
         PSK_TRY(cbf_window_fold(s, wbh.data(), (uint32_t)wbh.size(), st, &launched, &ok));
         if (launched && ok) {
-            ++s->win.folds;
-            ++g_window_folds;
+            __atomic_add_fetch(&g_window_folds, 1, __ATOMIC_RELAXED);
             PSK_TRY(account_weights(s, (const uint32_t *)nullptr, n_add, PSK_CTR_ADDED, (long long)s->k, st, true));
             return account_weights(s, (const uint32_t *)nullptr, n_rem, PSK_CTR_REMOVED, (long long)s->k, st, false);
         }
@@ -1481,7 +1452,7 @@ extern "C" int psk_cbf_add(psk_sketch *s, int layout, const void *data, const ui
     // (16-byte keys wait in the update window above; the other layouts here.  An append launches min(256, tiles) workgroups and workgroup i
     // always fills segment column i: batches of fewer than 256 tiles would pile the whole list into a few columns, which overflow long before
     // the list is full -- such batches take the direct kernel, as before round 3.)
-    if (!weights && g_auto_combine != 0 && s->win.n == 0 && s->comb.rem.n == 0 && s->comb.brem.n() == 0 && (int64_t)n >= g_part_min_keys &&
+    if (!weights && s->eff[HO_AUTO_COMBINE] != 0 && s->win.n == 0 && s->comb.rem.n == 0 && s->comb.brem.n() == 0 && (int64_t)n >= s->eff[HO_PART_MIN_KEYS] &&
         n >= (256u * 2048u * 7u) / (s->k ? s->k : 1u) && n * (uint64_t)s->k < s->m / 8 && g_auto_combine_keys > 0) {
         bool taken = false;
         PSK_TRY(scat_append(s, b, (uint64_t)g_auto_combine_keys, st, &taken));
@@ -1535,9 +1506,6 @@ static __global__ void k_book_removed(long long *ctr, const long long *tmp)
     if (blockIdx.x == 0 && threadIdx.x == 0) ctr[PSK_CTR_REMOVED] += tmp[PSK_CTR_REMOVED];
 }
 
-int64_t g_cbf_ordered_replays = 0;  // remove batches whose result depended on the order inside them: undone, replayed in order (tests)
-__thread int64_t g_remove_exact = 1;         // option "remove_exact": 0 = round 3's composition (clamps and tallies instead of replaying)
-
 // The validated remove (countingbloom.py:186-208) of a device-resident batch, as a TRANSACTION.  Unordered execution gives the
 // reference's table whenever the result does not depend on the order inside the batch; here that is CHECKED and, where it fails, the
 // batch is put back and executed in order:
@@ -1552,7 +1520,7 @@ __thread int64_t g_remove_exact = 1;         // option "remove_exact": 0 = round
 static int cbf_remove_exact(psk_sketch *s, const Batch &b, const uint32_t *w, hipStream_t st)
 {
     if (b.n == 0) return PSK_OK;
-    const bool big = part_wanted(b.n, s->k, 4);
+    const bool big = part_wanted(s, b.n, s->k, 4);
     if (!w && big) {
         // Unit weights into a big table: decrement optimistically (psk_nibble.hpp) -- if every counter holds at least as much as the
         // batch takes from it, every key is removed and one pass 1 + ONE pass over the table did it.  The verdict is one 4-byte
@@ -1616,7 +1584,7 @@ static int cbf_remove_exact(psk_sketch *s, const Batch &b, const uint32_t *w, hi
     }
     PSK_TRY(decrement(2, &part2));
     if (part1 != part2) return fail(PSK_EHIP, "transactional remove: the undo took another path than the decrement");
-    ++g_cbf_ordered_replays;
+    __atomic_add_fetch(&g_cbf_ordered_replays, 1, __ATOMIC_RELAXED);
     const int64_t *w64 = nullptr;
     if (w) {
         int64_t *dst = (int64_t *)(tmp + PSK_CTR_COUNT + 2);
@@ -1644,7 +1612,7 @@ static int cbf_remove_exact(psk_sketch *s, const Batch &b, const uint32_t *w, hi
 static int cbf_remove_device(psk_sketch *s, const Batch &b, const uint32_t *w, hipStream_t st)
 {
     if (b.n == 0) return PSK_OK;
-    if (g_remove_exact != 0) return cbf_remove_exact(s, b, w, st);
+    if (s->eff[HO_REMOVE_EXACT] != 0) return cbf_remove_exact(s, b, w, st);
     // (option "remove_exact" = 0, bench A/B: the one-kernel form -- per key: read the k counters, decide, subtract; exact for
     // well-formed batches, deviations tallied in PSK_CTR_VIOLATIONS)
     return with_source(b, [&](auto src) {
@@ -2201,10 +2169,8 @@ extern "C" int psk_scratch_bytes(psk_sketch *s, uint64_t bytes[3])
 // release the partition / staging scratch of a handle (hundreds of MB after a large batch); it regrows on demand
 extern "C" int psk_release_scratch(psk_sketch *s)
 {
-    if (!s) return fail(PSK_EINVAL, "sketch handle is NULL");
-    PSK_USE_DEVICE(s->device);
+    CHECK_HANDLE_RO(s, -1);
     if (s->pend.active) return fail(PSK_EINVAL, "a split lookup is pending: finish it before releasing the scratch buffers");
-    ho_apply(s);  // (what is waiting is applied under this sketch's own options)
     PSK_TRY(flush_combined(s, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     PSK_TRY(for_each_scratch(s, [](DevBuf &b, bool) {  // (the pinned pages stay: psk_destroy alone frees them)

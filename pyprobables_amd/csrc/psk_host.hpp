@@ -83,14 +83,15 @@ struct DevBuf {
 };
 constexpr uint64_t kPinBytes = 4096;
 
-// Per-sketch tunables (psk_sketch_set_option): the options below can differ between two sketches of one process.  The variables the
-// launchers read (g_part_min_keys ...) are THREAD-LOCAL effective values: every entry point that takes a handle sets them from the handle's
-// overrides, falling back to the process-wide defaults psk_set_option maintains (kHoUnset = inherit the default).
+// Per-sketch tunables (psk_sketch_set_option): the options below can differ between two sketches of one process.  The handle holds the
+// overrides (`opt`, kHoUnset = follow the default), the option table of psk_capi.hip the process defaults; every entry point that takes a
+// handle resolves them ONCE, on entry, into `eff` (CHECK_HANDLE_RO), and that is what the launchers read.
 enum HandleOpt { HO_PART_MIN_KEYS, HO_CBF_SHADOW, HO_AUTO_COMBINE, HO_WINDOW, HO_WINDOW_KEYS, HO_SCRATCH_BUDGET, HO_REMOVE_EXACT, HO_BLOOM_LOOKUP, HO_COUNT };
 constexpr int64_t kHoUnset = INT64_MIN;
 
 struct psk_sketch {
     int64_t opt[HO_COUNT] = {kHoUnset, kHoUnset, kHoUnset, kHoUnset, kHoUnset, kHoUnset, kHoUnset, kHoUnset};
+    int64_t eff[HO_COUNT] = {};  // the values in force for the call in progress (a handle is used by one thread at a time)
     bool table_private = false;  // option "table_private": the holder of a caller-owned table announces every outside write (psk_table_info / psk_rescan_bound)
     int kind;
     int device;
@@ -128,7 +129,7 @@ struct psk_sketch {
         bool grow_bound = true, weights_signed = false;
         bool weights01 = false;  // the weights are 0 / 1 flags (amounts of a validated unit-weight CBF remove): masked unit probes may serve
     } acct;
-    // Bloom lookups: which scheme the next large batch takes (g_bloom_lookup = 2, auto).  The kernels tally what they see
+    // Bloom lookups: which scheme the next large batch takes (option "bloom_lookup" = 2, auto).  The kernels tally what they see
     // (keyed: probes that missed; return trip: keys answered absent) into lk_dev; the tally is copied to a pinned host page
     // when the call ends and read -- without any synchronisation, so possibly one call late -- when the next one starts.
     struct {
@@ -197,7 +198,6 @@ struct psk_sketch {
         std::vector<WinBatch> batches;
         uint32_t backoff = 0;      // windows left that are replayed batch by batch without trying the fold (after a failed proof)
         void *pin = nullptr;       // pinned staging of the phase table
-        uint64_t folds = 0, replays = 0;   // statistics (psk_get_option "update_window_folds" / "_replays" report the globals)
     } win;
     DevBuf s_snap, s_wstat, s_phase;           // window fold: per-phase segment fill counts, per-part status, phase table
     PartGeom rm_g{};     // geometry of the validated remove's fast path between its optimistic decrement and a possible undo
@@ -230,6 +230,23 @@ struct psk_sketch {
 
 PSK_HIDDEN int ensure(DevBuf &b, uint64_t bytes);  // grow a scratch buffer
 
+// The handle gate: every entry point that works on a handle passes it, and it alone resolves the handle's options (psk_destroy, which
+// accepts NULL, calls resolve_options itself).
+PSK_HIDDEN void resolve_options(psk_sketch *s);  // psk_capi.hip, below the option table
+#define CHECK_HANDLE_RO(s, want_kind)                                                    \
+    do {                                                                                 \
+        if (!(s)) return fail(PSK_EINVAL, "sketch handle is NULL");                      \
+        if ((want_kind) >= 0 && (s)->kind != (want_kind))                                \
+            return fail(PSK_EINVAL, "wrong sketch kind %d for this call", (s)->kind);    \
+        resolve_options(s);                                                              \
+    } while (0);                                                                         \
+    PSK_USE_DEVICE((s)->device)
+// every entry point that may change the table (or hands its pointer out) moves the table's version on: what was derived from the
+// table -- psk_sketch::shadow, the 4-bit images of the nibble-slice lookup -- is stale from here on.  Read-only entries: _RO.
+#define CHECK_HANDLE(s, want_kind)                                                       \
+    CHECK_HANDLE_RO(s, want_kind);                                                       \
+    ++(s)->table_version
+
 static inline int grid_for_keys(uint64_t n)  // direct kernels: 256 CUs x 16 blocks, grid-stride beyond that
 {
     uint64_t g = (n + kBlock - 1) / kBlock;
@@ -240,19 +257,14 @@ static inline int grid_for_keys(uint64_t n)  // direct kernels: 256 CUs x 16 blo
 
 
 // ------------------------------------------------- partitioned (large-batch) path
-// Tunables (psk_set_option): the partitioned path is taken when the batch has at least g_part_min_keys keys and
-// the table geometry allows it; g_part_mode 0 = never, 1 = auto.
-extern PSK_HIDDEN __thread int64_t g_part_min_keys;
-extern PSK_HIDDEN int64_t g_part_mode, g_part_max_keys, g_part_cache_bytes, g_part_two_level_slices, g_part_debug;
-extern PSK_HIDDEN __thread int64_t g_bloom_lookup;      // Bloom lookups: 0 keyed probes + miss stores, 1 return trip (psk_lookup.hpp), 2 (default) by the observed miss rate
-extern PSK_HIDDEN int64_t g_part_tile_threads;   // pass 1 workgroup shape for k <= 8: 0 = auto (launch_scatter), 512 / 1024 = forced
-extern PSK_HIDDEN int64_t g_part_even_tiles;     // 1 (default): pass 1 evens the tile size out over the workgroups
-extern PSK_HIDDEN int64_t g_lookup_half;           // 1 (default): counter lookups into 2^26 .. 2^27 counters use 2^16-counter slices of 16-bit values
-extern PSK_HIDDEN int64_t g_small_weights;     // weighted CMS adds: 0 never the compact probe format, 1 by the hint, 2 always (tests)
-extern PSK_HIDDEN __thread int64_t g_cbf_shadow;         // keep the nibble-slice lookup's images of an unchanged table
-extern PSK_HIDDEN int64_t g_lookup_nibble, g_update_nibble;  // CBF tables beyond one level of 32-bit slices: 4-bit slice images (psk_nibble.hpp)
-extern PSK_HIDDEN int64_t g_part_dense_groups;   // pass 2 walks a wave's segments end to end when a segment holds fewer groups than this on average (0 = never)
-extern PSK_HIDDEN int64_t g_ragged_sort;         // option "ragged_sort": pass 1 hands keys of different lengths to its lanes in order of length (psk_partition.hpp sort_tile)
+// Process-wide options (psk_set_option): every variable is declared here and defined, with its default and meaning, above the
+// option table of psk_capi.hip.  (The per-sketch options are no variables: psk_sketch::eff.)
+extern PSK_HIDDEN int64_t g_part_mode, g_part_max_keys, g_part_cache_bytes, g_part_two_level_slices, g_part_debug, g_part_tile_threads,
+    g_part_even_tiles, g_part_dense_groups, g_part_bins, g_ragged_sort, g_lookup_half, g_lookup_nibble, g_update_nibble, g_nib_min_lg_lookup,
+    g_nib_min_lg_update, g_small_weights, g_remove_dryrun, g_combine_keys, g_auto_combine_keys, g_window_wide, g_window_tile,
+    g_window_force_fail, g_merge_single_rank, g_lazy_clear, g_host_poll_us,
+    // read-only counters (handles on different threads bump them: relaxed atomic adds)
+    g_cbf_ordered_replays, g_window_folds, g_window_replays, g_small_weights_used, g_cbf_shadow_hits, g_running_fast, g_running_sequential;
 
 // slices of a table of `cells` cells; max_shift = log2(cells one LDS slice may hold)
 // target_lg: aim at 2^target_lg .. 2^(target_lg+1)-1 slices.  8 (one slice per CU or more) for the Bloom tables; the counter
@@ -281,7 +293,6 @@ static inline bool part_slices(uint64_t cells, uint32_t max_shift, uint32_t min_
 // Geometry of the 4-bit slice images (psk_nibble.hpp): slices of 2^15 .. 2^18 counters, at least 256 of them when the table allows
 // (2^18 from 2^26 counters on: 1024 slices for BASELINE cfg 4's 2^28).  update = false: lookups (tables of 2^nibble_min_lg_lookup
 // counters and more), true: unit adds / decrements / write-combining segments (more than 2^nibble_min_lg_update counters).
-extern PSK_HIDDEN int64_t g_nib_min_lg_lookup, g_nib_min_lg_update;
 static inline bool nib_geometry(uint64_t cells, bool update, PartGeom *g)
 {
     if (update ? cells <= (1ULL << g_nib_min_lg_update) : cells < (1ULL << g_nib_min_lg_lookup)) return false;
@@ -353,7 +364,6 @@ struct src_fat512 { static constexpr bool value = std::is_same<Src, KeysFixed16>
 
 // ---- pass 1 through fixed-capacity bins (psk_part_bins.hpp, round 6): which (layout, payload, k) may take it, and its geometry
 // option "pass1_bins": 1 (default) = wherever eligible, 0 = k_part_scatter everywhere (A/B, tests)
-extern PSK_HIDDEN int64_t g_part_bins;
 template <class Src, class Pay, int KT>
 struct bins_eligible {
     static constexpr bool value = pay_bins_ok<Pay>::value && KT <= 8 && src_fat512<Src>::value;  // (the 16- and 8-byte layouts)
@@ -653,18 +663,18 @@ static int with_part_source(const Batch &b, bool *handled, F &&f)
 
 // `scale`: measured crossover vs the direct kernels (scripts/crossover.py, m = 2^28 / 2^20 x 5): Bloom insert wins
 // from ~64 K keys (scale 1), Bloom lookups and counter adds from ~256 K keys (scale 4)
-static inline bool part_wanted(uint64_t n, uint32_t k, int64_t scale = 1)
+static inline bool part_wanted(const psk_sketch *s, uint64_t n, uint32_t k, int64_t scale = 1)
 {
-    return g_part_mode != 0 && (int64_t)n >= g_part_min_keys * scale && k <= 32;
+    return g_part_mode != 0 && (int64_t)n >= s->eff[HO_PART_MIN_KEYS] * scale && k <= 32;
 }
 
 // Option "scratch_budget_bytes" (0 = none): caps the partition scratch of a handle by cutting a batch into more rounds.  per_key:
 // scratch bytes one key of a round occupies (bucket buffer incl. padding and slack, plus values / perm for lookups).
-extern PSK_HIDDEN __thread int64_t g_scratch_budget;
-static inline uint64_t cap_round_by_budget(uint64_t rk, double per_key)
+static inline uint64_t cap_round_by_budget(const psk_sketch *s, uint64_t rk, double per_key)
 {
-    if (g_scratch_budget <= 0 || per_key <= 0) return rk;
-    uint64_t cap = (uint64_t)((double)g_scratch_budget / per_key);
+    const int64_t budget = s->eff[HO_SCRATCH_BUDGET];
+    if (budget <= 0 || per_key <= 0) return rk;
+    uint64_t cap = (uint64_t)((double)budget / per_key);
     if (cap < (1u << 18)) cap = 1u << 18;  // (below ~256 K keys the per-round fixed costs dominate: the floor of the cap)
     return rk < cap ? rk : cap;
 }
@@ -674,7 +684,7 @@ static inline uint64_t cap_round_by_budget(uint64_t rk, double per_key)
 // 321 us, two rounds of 237 MB 271 us; inserts at 300 MB are still best in one round).  So a batch whose buffer
 // would exceed 1.5 x `partition_cache_bytes` is cut into equal rounds of at most that size.
 // group = probes per 16-byte group of the encoding in use.
-static inline uint64_t part_round_keys(uint64_t n, uint32_t k, int group)
+static inline uint64_t part_round_keys(const psk_sketch *s, uint64_t n, uint32_t k, int group)
 {
     uint64_t rk = (uint64_t)g_part_max_keys < n ? (uint64_t)g_part_max_keys : n;
     if (g_part_cache_bytes > 0 && n) {
@@ -687,27 +697,27 @@ static inline uint64_t part_round_keys(uint64_t n, uint32_t k, int group)
             if (per < rk) rk = per;
         }
     }
-    rk = cap_round_by_budget(rk, (double)k * 16.0 / group * 1.5);
+    rk = cap_round_by_budget(s, rk, (double)k * 16.0 / group * 1.5);
     return rk ? rk : 1;
 }
 
 // Big tables (>= 64 MiB): pass 2 reads (lookups) or read-modify-writes (updates) the WHOLE table once per round, which costs
 // more than what a cache-sized bucket buffer saves -- rounds as large as `partition_max_keys` allows
-static inline uint64_t part_round_keys_big_table(uint64_t n, uint32_t k, int group, uint64_t table_bytes)
+static inline uint64_t part_round_keys_big_table(const psk_sketch *s, uint64_t n, uint32_t k, int group, uint64_t table_bytes)
 {
-    const uint64_t rk = part_round_keys(n, k, group);
+    const uint64_t rk = part_round_keys(s, n, k, group);
     if (table_bytes < (64ULL << 20)) return rk;
     uint64_t big = (uint64_t)g_part_max_keys < n ? (uint64_t)g_part_max_keys : n;
-    big = cap_round_by_budget(big, (double)k * 16.0 / group * 1.5);
+    big = cap_round_by_budget(s, big, (double)k * 16.0 / group * 1.5);
     return big > rk ? big : rk;
 }
 
 // Rounds of the two-level path: every round ends in a fold that read-modify-writes the WHOLE table (0.5 ms for 1 GiB),
 // which dwarfs what a cache-sized bucket buffer saves -- as few rounds as `partition_max_keys` allows
-static inline uint64_t part_round_keys_two_level(uint64_t n, uint32_t k = 7)
+static inline uint64_t part_round_keys_two_level(const psk_sketch *s, uint64_t n, uint32_t k = 7)
 {
     uint64_t rk = (uint64_t)g_part_max_keys < n ? (uint64_t)g_part_max_keys : n;
-    rk = cap_round_by_budget(rk, (double)k * (4.0 + 4.0) * 1.5);  // two bucket buffers (level 1: 4 B per probe, level 2: up to 4)
+    rk = cap_round_by_budget(s, rk, (double)k * (4.0 + 4.0) * 1.5);  // two bucket buffers (level 1: 4 B per probe, level 2: up to 4)
     return rk ? rk : 1;
 }
 
@@ -807,9 +817,3 @@ struct WinBatchHost {   // one waiting batch, in arrival order: n 16-byte keys a
     uint32_t remove;
 };
 PSK_DECLARE_VARIANTS(int, cbf_window_fold, (psk_sketch *s, const WinBatchHost *wb, uint32_t nb, hipStream_t st, bool *launched, bool *ok))
-extern PSK_HIDDEN __thread int64_t g_remove_exact, g_window, g_window_keys;
-extern PSK_HIDDEN int64_t g_cbf_ordered_replays;
-extern PSK_HIDDEN int64_t g_window_folds, g_window_replays, g_window_force_fail;
-extern PSK_HIDDEN int64_t g_remove_dryrun;
-extern PSK_HIDDEN __thread int64_t g_auto_combine;
-extern PSK_HIDDEN int64_t g_auto_combine_keys, g_combine_keys;

@@ -121,16 +121,11 @@ int launch_grid(uint64_t n)
 
 }  // namespace
 
-extern PSK_HIDDEN int64_t g_merge_single_rank;
-int64_t g_merge_single_rank = 0;  // psk_set_option("merge_single_rank", 1): run the collective path even with one rank (tests)
-
 extern "C" int psk_merge_or(psk_sketch *s, void *nccl_comm, void *stream)
 {
-    if (!s) return fail(PSK_EINVAL, "sketch handle is NULL");
+    CHECK_HANDLE(s, -1);  // (the merge rewrites the table)
     if (s->kind != PSK_KIND_BLOOM) return fail(PSK_EINVAL, "psk_merge_or merges Bloom filters (counters: psk_merge_sum)");
     if (!nccl_comm) return fail(PSK_EINVAL, "communicator is NULL");
-    PSK_USE_DEVICE(s->device);
-    ++s->table_version;  // the merge rewrites the table (psk_sketch::shadow is stale from here on)
     PSK_TRY(clear_materialize(s, (hipStream_t)stream));  // (a deferred clear lands before the exchange reads the table)
     Rccl *R;
     PSK_TRY(rccl(&R));
@@ -166,11 +161,9 @@ extern "C" int psk_merge_or(psk_sketch *s, void *nccl_comm, void *stream)
 
 extern "C" int psk_merge_sum(psk_sketch *s, void *nccl_comm, void *stream)
 {
-    if (!s) return fail(PSK_EINVAL, "sketch handle is NULL");
+    CHECK_HANDLE(s, -1);  // (the merge rewrites the table; the updates it flushes below go under this sketch's options)
     if (s->kind == PSK_KIND_BLOOM) return fail(PSK_EINVAL, "psk_merge_sum merges counter tables (Bloom: psk_merge_or)");
     if (!nccl_comm) return fail(PSK_EINVAL, "communicator is NULL");
-    PSK_USE_DEVICE(s->device);
-    ++s->table_version;  // the merge rewrites the table (psk_sketch::shadow is stale from here on)
     Rccl *R;
     PSK_TRY(rccl(&R));
     ncclComm_t comm = (ncclComm_t)nccl_comm;

@@ -7,7 +7,7 @@ static_assert(kBloomApplyCtrWords == PSK_CTR_COUNT, "k_bloom_apply's store mode 
 int PSK_VARIANT(bloom_add_partitioned)(psk_sketch *s, const Batch &b, hipStream_t st, bool *done)
 {
     *done = false;
-    if (!part_wanted(b.n, s->k)) return PSK_OK;
+    if (!part_wanted(s, b.n, s->k)) return PSK_OK;
     PartGeom g;
     if (!part_slices(s->m, 20, 7, &g, 16384)) return PSK_OK;
     g.k = s->k;
@@ -16,7 +16,7 @@ int PSK_VARIANT(bloom_add_partitioned)(psk_sketch *s, const Batch &b, hipStream_
     if (two_level_geometry(g, &g1, &sub_bits)) {
         PSK_TRY(clear_materialize(s, st));  // (the store mode serves the single-level path only)
         // more slices than one pass can bin well: coarse buckets first (inline 32-bit probes), then k_part_split
-        const uint64_t round_keys = part_round_keys_two_level(b.n, s->k);
+        const uint64_t round_keys = part_round_keys_two_level(s, b.n, s->k);
         for (uint64_t start = 0; start < b.n; start += round_keys) {
             const uint64_t cnt = b.n - start < round_keys ? b.n - start : round_keys;
             const Batch sub = sub_batch(b, start, cnt);
@@ -43,7 +43,7 @@ int PSK_VARIANT(bloom_add_partitioned)(psk_sketch *s, const Batch &b, hipStream_
         return PSK_OK;
     }
     if (g.nbuckets > (uint32_t)kPartMaxBuckets) return PSK_OK;
-    const uint64_t round_keys = part_round_keys_big_table(b.n, s->k, PayNone::group, s->padded_bytes);
+    const uint64_t round_keys = part_round_keys_big_table(s, b.n, s->k, PayNone::group, s->padded_bytes);
     // a deferred clear (psk_clear) is consumed by the first round: its apply stores the slices instead of read-modify-writing them, and
     // pass 1's spills wait in a list (they would be overwritten in the table) -- one entry per probe at most, so the list is exact
     BloomApplyStore first;

@@ -38,10 +38,10 @@ static int check_round_test(psk_sketch *s, const PartGeom &g, uint8_t *out, hipS
 static bool check_geometry(psk_sketch *s, const Batch &b, PartGeom *g, uint64_t *round_keys)
 {
     const uint64_t n = b.n;
-    if (!part_wanted(n, s->k, 4)) return false;
+    if (!part_wanted(s, n, s->k, 4)) return false;
     if (!part_slices(s->m, 20, 7, g)) return false;
     g->k = s->k;
-    uint64_t rk = part_round_keys_big_table(n, s->k, PayKeyId::group, s->padded_bytes);
+    uint64_t rk = part_round_keys_big_table(s, n, s->k, PayKeyId::group, s->padded_bytes);
     // a keyed group spells the tile's ordinal inside its workgroup in 4 bits: at most 16 tiles per workgroup and round
     // (256 workgroups x 16 x 2048-key tiles for k <= 8; 512-key tiles beyond)
     uint64_t cap = (uint64_t)PayKeyId::max_tiles_per_wg * (keyed_wgs(*g) ? keyed_wgs(*g) : 256u) *
@@ -69,7 +69,7 @@ static bool check_geometry(psk_sketch *s, const Batch &b, PartGeom *g, uint64_t 
 static int bloom_check_return_trip(psk_sketch *s, const Batch &b, uint8_t *out_dev, hipStream_t st, bool *done)
 {
     *done = false;
-    if (!part_wanted(b.n, s->k, 4)) return PSK_OK;
+    if (!part_wanted(s, b.n, s->k, 4)) return PSK_OK;
     PartGeom g;
     if (!part_slices(s->m, 20, 7, &g)) return PSK_OK;
     g.k = s->k;
@@ -134,10 +134,10 @@ static int bloom_check_return_trip(psk_sketch *s, const Batch &b, uint8_t *out_d
 // geometry and round size of a tile-flag lookup of b; false: not eligible
 static bool tile_flag_geometry(psk_sketch *s, const Batch &b, PartGeom *g, uint64_t *round_keys_out)
 {
-    if (!part_wanted(b.n, s->k, 4)) return false;
+    if (!part_wanted(s, b.n, s->k, 4)) return false;
     if (!part_slices(s->m, 20, 7, g)) return false;
     g->k = s->k;
-    uint64_t round_keys = part_round_keys_big_table(b.n, s->k, PayTileTag::group, s->padded_bytes);
+    uint64_t round_keys = part_round_keys_big_table(s, b.n, s->k, PayTileTag::group, s->padded_bytes);
     // 4 bits of tile ordinal per group: at most 16 tiles per pass-1 workgroup and round
     bool handled = false;
     uint64_t cap = 0;
@@ -214,7 +214,7 @@ static int tile_flag_test(psk_sketch *s, const Batch &sub, uint64_t cnt, const P
         HIP_TRY(hipGetLastError());
         const uint64_t ntiles = (cnt + g.tile - 1) / g.tile;
         LookupPublish pub;
-        if (publish_units && g_bloom_lookup == 2 && s->lk.dev) pub = LookupPublish{s->lk.dev, s->lk.pin, publish_units, 3};
+        if (publish_units && s->eff[HO_BLOOM_LOOKUP] == 2 && s->lk.dev) pub = LookupPublish{s->lk.dev, s->lk.pin, publish_units, 3};
         // (a small grid: with no tile flagged -- the usual case of the batches this scheme is chosen for -- every workgroup leaves at once, and
         // the launch is what remains of the kernel; 1024 workgroups cost ~5 us for nothing)
         hipLaunchKernelGGL((k_bloom_flag_resolve<Src, kTuPow2>), dim3((unsigned)(ntiles < kResolveWgs ? ntiles : kResolveWgs)), dim3(kResolveThreads), 0, st, src,
@@ -314,7 +314,7 @@ static int bloom_check_lazy(psk_sketch *s, const Batch &b, uint8_t *out_dev, hip
     PSK_TRY(with_part_source(b, &handled, [&](auto src) {
         using Src = decltype(src);
         const dim3 grid((unsigned)grid_for_keys(b.n)), block(kBlock);
-        unsigned long long *ctr = g_bloom_lookup == 2 ? s->lk.dev : nullptr;
+        unsigned long long *ctr = s->eff[HO_BLOOM_LOOKUP] == 2 ? s->lk.dev : nullptr;
         if constexpr (kTuPow2) {
             if (s->m <= (1ULL << 32))
                 hipLaunchKernelGGL((k_bloom_check_lazy<Src, true, true>), grid, block, 0, st, src, (const uint32_t *)s->table, s->md, s->k, b.n, out_dev, ctr);
@@ -336,7 +336,7 @@ static int bloom_check_lazy(psk_sketch *s, const Batch &b, uint8_t *out_dev, hip
 // call late, and the very first call is keyed).
 static int choose_scheme(psk_sketch *s, hipStream_t st)
 {
-    if (g_bloom_lookup != 2) return (int)g_bloom_lookup;   // forced: 0 keyed, 1 return trip, 3 tile flags, 4 lazy gathers
+    if (s->eff[HO_BLOOM_LOOKUP] != 2) return (int)s->eff[HO_BLOOM_LOOKUP];   // forced: 0 keyed, 1 return trip, 3 tile flags, 4 lazy gathers
     if (!s->lk.dev) {
         HIP_TRY(hipMalloc((void **)&s->lk.dev, 8));
         void *pin = nullptr;
@@ -389,7 +389,7 @@ static int publish_tally(psk_sketch *s, unsigned long long units, int scheme, hi
 {
     // (every call: the one-thread launch is hidden behind the call's last kernel -- publishing only every fourth call measured the same
     // step time, 46.0-46.5 G key-ops/s either way, as did folding it into the last workgroup of k_bloom_test in round 2)
-    if (g_bloom_lookup != 2 || !s->lk.dev) return PSK_OK;
+    if (s->eff[HO_BLOOM_LOOKUP] != 2 || !s->lk.dev) return PSK_OK;
     hipLaunchKernelGGL(k_lookup_publish, dim3(1), dim3(1), 0, st, s->lk.dev, s->lk.pin, units, (unsigned long long)scheme);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
@@ -398,7 +398,7 @@ static int publish_tally(psk_sketch *s, unsigned long long units, int scheme, hi
 int PSK_VARIANT(bloom_check_partitioned)(psk_sketch *s, const Batch &b, uint8_t *out_dev, hipStream_t st, bool *done)
 {
     *done = false;
-    if (!part_wanted(b.n, s->k, 4)) return PSK_OK;
+    if (!part_wanted(s, b.n, s->k, 4)) return PSK_OK;
     const int scheme = choose_scheme(s, st);
     if (scheme < 0) return scheme;
     if (scheme == 1) {
@@ -441,7 +441,7 @@ int PSK_VARIANT(bloom_check_begin_partitioned)(psk_sketch *s, const Batch &b, hi
     s->pend.scattered = false;
     s->pend.b = b;
     s->pend.scheme = 0;
-    if (!part_wanted(b.n, s->k, 4)) return PSK_OK;
+    if (!part_wanted(s, b.n, s->k, 4)) return PSK_OK;
     const int scheme = choose_scheme(s, st);
     if (scheme < 0) return scheme;
     if (scheme == 3 && tile_flag_geometry(s, b, &s->pend.g, &s->pend.round_keys)) {

@@ -8,7 +8,7 @@ int PSK_VARIANT(cbf_unit_multi_partitioned)(psk_sketch *s, const void *const *ba
 {
     *done = false;
     const uint64_t cells = s->m;
-    if (g_update_nibble == 0 || n == 0 || n > part_round_keys_two_level(n, s->k) || !nib_load_ok(n, s->k, cells)) return PSK_OK;
+    if (g_update_nibble == 0 || n == 0 || n > part_round_keys_two_level(s, n, s->k) || !nib_load_ok(n, s->k, cells)) return PSK_OK;
     PartGeom g;
     if (!nib_geometry(cells, true, &g)) return PSK_OK;
     g.k = s->k;

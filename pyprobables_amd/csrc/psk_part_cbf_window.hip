@@ -2,9 +2,6 @@
 #include "psk_part_counter.hpp"
 #include "psk_window.hpp"
 
-extern PSK_HIDDEN int64_t g_window_wide;   // option "update_window_wide"
-extern PSK_HIDDEN int64_t g_window_tile;   // option "update_window_tile": 0 = by the rule in window_scatter, 2048 / 4096 = forced (A/B)
-
 // Tables of the window's pass 1 and fold (pinned staging + device copy, one contiguous upload): [0 .. kWinMaxPhases] the fold's phases,
 // behind them the pieces of pass 1 (PhaseDesc in psk_partition.hpp).
 constexpr size_t kWinMaxPieces = 4096 + 2 * kWinMaxPhases;   // (kWinMaxBatches waiting batches, each cut at most once more per phase end)

@@ -50,8 +50,6 @@ static inline int tally_args(psk_sketch *s, const PayWeight &pay, uint32_t nwg, 
     return PSK_OK;
 }
 
-extern PSK_HIDDEN int64_t g_small_weights_used;
-
 // the compact probe format for this weighted batch?  (exact either way: a weight outside 0 .. 15 goes to the table directly -- at the atomics'
 // rate, hence the hint: the count of such weights pass 1 of the previous batches saw)
 static inline bool small_weights_wanted(psk_sketch *s)
@@ -123,13 +121,13 @@ static inline int cbf_unit_nibble(psk_sketch *s, const Batch &b, const uint32_t 
 {
     *done = false;
     const uint64_t cells = s->m;
-    if (g_update_nibble == 0 || !part_wanted(b.n, s->k, 4)) return PSK_OK;
+    if (g_update_nibble == 0 || !part_wanted(s, b.n, s->k, 4)) return PSK_OK;
     if (b.n * (uint64_t)s->k < cells / 8) return PSK_OK;
     PartGeom g;
     if (!nib_geometry(cells, true, &g)) return PSK_OK;
     g.k = s->k;
     if (!nib_load_ok(b.n, s->k, cells)) return PSK_OK;  // (more than ~2.5 probes per counter: the 32-bit slices take the batch)
-    const uint64_t round_keys = part_round_keys_two_level(b.n, s->k);
+    const uint64_t round_keys = part_round_keys_two_level(s, b.n, s->k);
     for (uint64_t start = 0; start < b.n; start += round_keys) {
         const uint64_t cnt = b.n - start < round_keys ? b.n - start : round_keys;
         bool handled = false;
@@ -148,7 +146,7 @@ static inline int counter_add_partitioned(psk_sketch *s, const Batch &b, const u
                                    bool *done, int opt = 0, uint32_t *flag = nullptr)
 {
     *done = false;
-    if (!part_wanted(b.n, s->k, 4)) return PSK_OK;
+    if (!part_wanted(s, b.n, s->k, 4)) return PSK_OK;
     if constexpr (!SIGNED) {  // CountingBloomFilter: unit weights (or 0 / 1 amounts) into a big table -> nibble deltas, one level
         if (!w_dev || s->acct.weights01) {
             PSK_TRY(cbf_unit_nibble<NEG>(s, b, w_dev, st, done, opt, flag));
@@ -167,7 +165,7 @@ static inline int counter_add_partitioned(psk_sketch *s, const Batch &b, const u
         // Pass 2 read-modify-writes every slice of the table: only worth it when the batch brings enough probes
         // (direct atomics into a 1 GiB table run at ~20 G/s; the table RMW at ~4 TB/s)
         if (b.n * (uint64_t)s->k < cells / 8) return PSK_OK;
-        const uint64_t round_keys = part_round_keys_two_level(b.n, s->k);
+        const uint64_t round_keys = part_round_keys_two_level(s, b.n, s->k);
         SpillCounter<SIGNED> spill{(uint32_t *)s->table, w_dev == nullptr, NEG, sat2, flag, opt};
         TallyArgs ta2{};
         ta2.opt = (uint32_t)opt;
@@ -214,7 +212,7 @@ static inline int counter_add_partitioned(psk_sketch *s, const Batch &b, const u
     bool small_fmt = false;
     if constexpr (SIGNED && !NEG) small_fmt = w_dev != nullptr && cells < (1ULL << kSmallWeightShift) && g.shift <= 15 && small_weights_wanted(s);
     const bool small_asked = small_fmt;
-    const uint64_t round_keys = part_round_keys_big_table(b.n, s->k, w_dev ? (small_fmt ? PayWeightSmall::group : PayWeight::group) : PayUnit::group, s->padded_bytes);
+    const uint64_t round_keys = part_round_keys_big_table(s, b.n, s->k, w_dev ? (small_fmt ? PayWeightSmall::group : PayWeight::group) : PayUnit::group, s->padded_bytes);
     unsigned long long *sat = (unsigned long long *)(s->ctr + PSK_CTR_SATURATED);
     for (uint64_t start = 0; start < b.n; start += round_keys) {
         const uint64_t cnt = b.n - start < round_keys ? b.n - start : round_keys;
@@ -269,7 +267,7 @@ static inline int counter_add_partitioned(psk_sketch *s, const Batch &b, const u
         HIP_TRY(hipGetLastError());
     }
     if (w_dev) s->acct.pending = false;  // pass 1 summed the weights
-    if (small_asked && small_fmt) ++g_small_weights_used;  // (calls that travelled in the compact format; option "cms_small_weights_used": tests)
+    if (small_asked && small_fmt) __atomic_add_fetch(&g_small_weights_used, 1, __ATOMIC_RELAXED);  // (calls that travelled in the compact format; option "cms_small_weights_used": tests)
     *done = true;
     return PSK_OK;
 }

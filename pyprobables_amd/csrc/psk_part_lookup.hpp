@@ -5,15 +5,13 @@
 #include "psk_lookup.hpp"
 #include "psk_nibble.hpp"
 
-extern PSK_HIDDEN int64_t g_cbf_shadow_hits;  // nibble-slice lookups that loaded kept images (psk_sketch::shadow)
-
 // Keys per round.  Measured on MI355X (10 M CMS lookups): one round of 10 M keys 432 us, two 446, three cache-sized ones 464
 // -- the three kernels of a round stream ~50 B per key once and every round re-reads the table, so unlike the update
 // paths (part_round_keys) rounds are only cut at `partition_max_keys`.
-static inline uint64_t lookup_round_keys(uint64_t n, uint32_t k)
+static inline uint64_t lookup_round_keys(const psk_sketch *s, uint64_t n, uint32_t k)
 {
     uint64_t rk = (uint64_t)g_part_max_keys < n ? (uint64_t)g_part_max_keys : n;
-    rk = cap_round_by_budget(rk, (double)k * (2.0 + 4.0) * 1.5 + 4.0 * ((k + 1) / 2) + 8.0);  // probes + values + perm + runinfo
+    rk = cap_round_by_budget(s, rk, (double)k * (2.0 + 4.0) * 1.5 + 4.0 * ((k + 1) / 2) + 8.0);  // probes + values + perm + runinfo
     // pass 3 addresses a run's values by a 32-bit unit index (k_lookup_collect's run descriptors): at most 2^31 probes per round keeps the
     // round's groups, pads included, far below 2^31
     const uint64_t by_probes = (1ULL << 31) / (k ? k : 1);
@@ -28,7 +26,7 @@ static inline int counter_check_partitioned(psk_sketch *s, const Batch &b, uint3
                                             typename Query::Out *out_dev, hipStream_t st, bool *done, Redo &&redo)
 {
     *done = false;
-    if (!part_wanted(b.n, kk, 4)) return PSK_OK;
+    if (!part_wanted(s, b.n, kk, 4)) return PSK_OK;
     PartGeom g;
     // 2^15 counters = 128 KiB per slice.  Beyond 2048 such slices (2^26 counters: a CBF for 7 M elements at 1 %) and up to 2^27
     // counters: slices of 2^16 counters held as 16-bit values (k_counter_gather<true>; a counter at or above 2^16 raises the redo
@@ -39,7 +37,7 @@ static inline int counter_check_partitioned(psk_sketch *s, const Batch &b, uint3
         half = true;
     }
     g.k = kk;
-    const uint64_t round_keys = lookup_round_keys(b.n, kk);
+    const uint64_t round_keys = lookup_round_keys(s, b.n, kk);
     PSK_TRY(ensure(s->s_flag, 8));
     uint32_t *flag = (uint32_t *)s->s_flag.p;
     HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
@@ -126,7 +124,7 @@ static inline int cbf_check_nibble(psk_sketch *s, const Batch &b, uint32_t kk, u
 {
     *done = false;
     const uint64_t cells = s->m;
-    if (g_lookup_nibble == 0 || !part_wanted(b.n, kk, 4)) return PSK_OK;
+    if (g_lookup_nibble == 0 || !part_wanted(s, b.n, kk, 4)) return PSK_OK;
     // pass 2 reads the WHOLE table (4 B per counter at ~4.4 TB/s: 0.25 ms for 2^28 counters) where the direct kernel fetches one
     // 64-byte line per probe (52 G probes/s): worth it from about cells / 16 probes on (measured on the 1 GiB table: a 0.5 M-key
     // lookup 67 us direct, 0.4 ms through the slices)
@@ -136,9 +134,9 @@ static inline int cbf_check_nibble(psk_sketch *s, const Batch &b, uint32_t kk, u
     const uint64_t shadow_words = (uint64_t)g.nbuckets << (g.shift - 3);
     // (with the table's 4-bit images at hand -- psk_sketch::shadow, below -- the pass reads 1/8 of that: from cells / 64 probes on;
     // measured on the 1 GiB table: 1 M keys 134 us direct, ~75 us through kept images)
-    const bool shadow_ready = g_cbf_shadow != 0 && s->shadow.allow && s->shadow.built == s->table_version && s->shadow.words == shadow_words &&
+    const bool shadow_ready = s->eff[HO_CBF_SHADOW] != 0 && s->shadow.allow && s->shadow.built == s->table_version && s->shadow.words == shadow_words &&
                               s->shadow.stream == st && s->shadow.img.p != nullptr;
-    const bool may_shadow = g_cbf_shadow != 0 && s->shadow.allow;
+    const bool may_shadow = s->eff[HO_CBF_SHADOW] != 0 && s->shadow.allow;
     if (may_shadow) {  // lookups in a row that found this version of the table (this one included)
         if (s->shadow.seen == s->table_version) ++s->shadow.seen_count;
         else s->shadow.seen = s->table_version, s->shadow.seen_count = 1;
@@ -150,7 +148,7 @@ static inline int cbf_check_nibble(psk_sketch *s, const Batch &b, uint32_t kk, u
         if (probes < cells / 64) return PSK_OK;
         if (probes < cells / 16 && !shadow_ready && !(may_shadow && s->shadow.seen_count >= 3)) return PSK_OK;
     }
-    const uint64_t round_keys = lookup_round_keys(b.n, kk);
+    const uint64_t round_keys = lookup_round_keys(s, b.n, kk);
     PSK_TRY(ensure(s->s_flag, 8));
     uint32_t *flag = (uint32_t *)s->s_flag.p, *amb = flag + 1;  // [0] a segment overflowed, [1] a key's answer is ambiguous (15)
     HIP_TRY(hipMemsetAsync(flag, 0, 8, st));
@@ -159,7 +157,7 @@ static inline int cbf_check_nibble(psk_sketch *s, const Batch &b, uint32_t kk, u
     bool shadow_used = false;
     const uint32_t *shadow_in = nullptr;
     uint32_t *shadow_out = nullptr;
-    if (g_cbf_shadow != 0 && s->shadow.allow) {
+    if (s->eff[HO_CBF_SHADOW] != 0 && s->shadow.allow) {
         if (shadow_ready) {
             shadow_in = (const uint32_t *)s->shadow.img.p;
         } else if (b.n > round_keys || s->shadow.seen_count >= 2) {
@@ -209,7 +207,7 @@ static inline int cbf_check_nibble(psk_sketch *s, const Batch &b, uint32_t kk, u
         }));
         if (!handled || !fits) return PSK_OK;  // (only ever on the first round: nothing was launched)
     }
-    if (shadow_used) ++g_cbf_shadow_hits;  // (calls that loaded the images; option "cbf_lookup_shadow_hits": tests)
+    if (shadow_used) __atomic_add_fetch(&g_cbf_shadow_hits, 1, __ATOMIC_RELAXED);  // (calls that loaded the images; option "cbf_lookup_shadow_hits": tests)
     PSK_TRY(recheck(amb, st));  // keys whose counters are all 15 or more: answered from the table itself (flag-guarded)
     PSK_TRY(redo(flag, st));     // a segment overflowed: exact redo of the batch by the direct kernel (flag-guarded)
     *done = true;
