@@ -338,6 +338,57 @@ int psk_qf_decode(uint32_t q, const void *filter_dev, const uint32_t *occupied_d
                   const uint32_t *shifted_dev, int64_t *word_counts_dev, uint32_t *marks_dev, uint32_t *out_dev, uint64_t out_cap,
                   int device, void *stream);
 
+/* ------------------------------------------------------------ CuckooFilter
+ * cuckoo/cuckoo.py: `capacity` buckets of `bucket_size` fingerprints of `fp_bits` bits.  No handle: the caller owns (device memory)
+ *   buckets   uint32[capacity][bucket_size], every row filled from the left, its unused slots 0 (an export is this array plus the footer)
+ *   fill      uint32[capacity], the fingerprints in each row (fingerprint 0 is legal, so the zeros do not say it)
+ * 1 <= capacity < 2^31, bucket_size >= 1, 1 <= fp_bits <= 32.  A key is the triple fp = fnv_1a(key) & (2^fp_bits - 1),
+ * idx_1 = fp % capacity, idx_2 = fnv_1a(str(fp)) % capacity (cuckoo.py:483-506); `triples` is uint32[3][n]: the fps, the idx_1s, the idx_2s.
+ * Every call leaves the table exactly as the reference's loop over the same keys would (DESIGN.md "Cuckoo filter").
+ *   triples      out[3][n] of the keys; PSK_KEYS_HASHES rows carry fnv_1a(key), or a fingerprint itself (the re-insert stream of
+ *                _expand_logic, cuckoo.py:455-481); `where` as everywhere (out follows the keys)
+ *   check        out[i] = 0 / 1, check(key_i) (cuckoo.py:306-315, :440-446), hash and lookup in one kernel
+ *   present      the same for device triples
+ *   place_sweep / place_apply   the part of `for t in triples: _insert_fingerprint(t)` (cuckoo.py:361-368) in front of the first key that
+ *                needs a kick, for triples that are neither in the table nor repeated (the caller's job: present + any sort).
+ *                claims_dev: the 2m values idx << 32 | j << 1 | which (which = 0: idx_1 of key j, 1: idx_2) in ascending order,
+ *                pos_dev[which * m + j]: where that claim stands.  d_in / d_out: one byte per key, 1 / 2 = goes to idx_1 / idx_2,
+ *                3 = needs a kick; start from all 1 and sweep with the two buffers swapped.  Each sweep sets marks_dev[0] to the first key
+ *                whose decision changed (0xFFFFFFFF: none) and marks_dev[1] to the first key that decided 3: keys in front of marks[0]
+ *                are final (the sweep that changed nothing in front of e proves [0, e): a triangular system has one fixed point).
+ *                place_apply writes the keys [0, prefix) by the decisions d_dev, prefix <= min(marks) of the last sweep, and counts
+ *                them into fill.  Enqueue only.
+ *   insert       triples [start, end) one after the other by ONE lane: add (dedup != 0: skip a fingerprint found in its two rows,
+ *                cuckoo.py:291-304) or the re-insert of an expansion (dedup = 0), kicks included (cuckoo.py:361-392).  The kicks draw from
+ *                the MT19937 in mt_state_dev: the 625 words of Python's random.getstate()[1], read at the start, written back at the end,
+ *                so random.setstate() with them leaves `random` where the reference would.  Stops early after `budget` steps (a key and a
+ *                swap are one step each; bounds the launch, budget >= 1) or at a failed walk, whose swaps stay.  result_dev[12], in and
+ *                out: [0] 0 = stopped at end / at the budget in front of key [1], 1 = the walk of key [1] failed, 2 = bad arguments in
+ *                device memory (indices outside the table), 3 = the budget ran out INSIDE the walk of key [1]; [1] the first key not
+ *                done, [2] the fingerprint left over, [3] fingerprints newly counted, [4] keys that began to walk, [5] steps used,
+ *                [6..8] the suspended walk (fingerprint in hand, row, swaps done).  Pass [0] = 0 on entry -- or, to take a suspended walk
+ *                up, the words of the launch that returned 3, with start = its [1].  Enqueue only.
+ *   remove       out[i] = remove(key_i) in order (cuckoo.py:317-330) for device triples: rank_dev[i] = how many earlier requests of the batch
+ *                carry the same fingerprint (any stable sort).  bucket_size <= 32.  row_marks_dev: uint32[capacity], zero on entry and
+ *                zero again afterwards.  Rows are compacted to the left, vacated slots zeroed, fill lowered.  Enqueue only. */
+int psk_ck_triples(uint64_t capacity, uint32_t fp_bits, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len,
+                   int where, uint32_t *out, int device, void *stream);
+int psk_ck_check(uint64_t capacity, uint32_t bucket_size, uint32_t fp_bits, const uint32_t *buckets_dev, const uint32_t *fill_dev, int layout,
+                 const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, uint8_t *out, int device, void *stream);
+int psk_ck_present(uint64_t capacity, uint32_t bucket_size, const uint32_t *buckets_dev, const uint32_t *fill_dev,
+                   const uint32_t *triples_dev, uint64_t n, uint8_t *out_dev, int device, void *stream);
+int psk_ck_place_sweep(uint64_t capacity, uint32_t bucket_size, const uint32_t *fill_dev, const uint32_t *triples_dev,
+                       const uint64_t *claims_dev, const uint32_t *pos_dev, uint64_t m, const uint8_t *d_in_dev, uint8_t *d_out_dev,
+                       uint32_t *marks_dev, int device, void *stream);
+int psk_ck_place_apply(uint64_t capacity, uint32_t bucket_size, uint32_t *buckets_dev, uint32_t *fill_dev, const uint32_t *triples_dev,
+                       const uint64_t *claims_dev, const uint32_t *pos_dev, uint64_t m, const uint8_t *d_dev, uint64_t prefix, int device,
+                       void *stream);
+int psk_ck_insert(uint64_t capacity, uint32_t bucket_size, uint32_t max_swaps, uint32_t *buckets_dev, uint32_t *fill_dev,
+                  const uint32_t *triples_dev, uint64_t n, uint64_t start, uint64_t end, int dedup, uint64_t budget,
+                  uint32_t *mt_state_dev, uint32_t *result_dev, int device, void *stream);
+int psk_ck_remove(uint64_t capacity, uint32_t bucket_size, uint32_t *buckets_dev, uint32_t *fill_dev, const uint32_t *triples_dev,
+                  const uint32_t *rank_dev, uint64_t n, uint32_t *row_marks_dev, uint8_t *out_dev, int device, void *stream);
+
 /* ------------------------------------------------------ table algebra (device pointers)
  * Streaming kernels over whole tables; also the local half of the multi-GPU merge.
  * or/and: bloom.py:371-428 union/intersection;  popcount: bloom.py:552-557;

@@ -2,7 +2,7 @@
 
 Drop-in names for the accelerated path (reference ``probables/__init__.py:3-53``):
 ``BloomFilter``, ``CountingBloomFilter``, ``CountMinSketch`` (+ ``CountMeanSketch`` /
-``CountMeanMinSketch``, ``HeavyHitters``, ``StreamThreshold``), ``ExpandingBloomFilter`` / ``RotatingBloomFilter``, ``QuotientFilter``, their exceptions and the ``hash_function`` helpers.  Tables live in GPU HBM,
+``CountMeanMinSketch``, ``HeavyHitters``, ``StreamThreshold``), ``ExpandingBloomFilter`` / ``RotatingBloomFilter``, ``QuotientFilter``, ``CuckooFilter``, their exceptions and the ``hash_function`` helpers.  Tables live in GPU HBM,
 the work is done by hand-written gfx950 HIP kernels behind the C ABI in ``include/psk.h``.
 """
 
@@ -12,6 +12,7 @@ from .countminsketch import CountMeanMinSketch, CountMeanSketch, CountMinSketch,
 from .expandingbloom import ExpandingBloomFilter, RotatingBloomFilter
 from .exceptions import (
     CountMinSketchError,
+    CuckooFilterFullError,
     InitializationError,
     NativeLibraryError,
     NotSupportedError,
@@ -21,6 +22,7 @@ from .exceptions import (
     SimilarityError,
 )
 from .quotientfilter import QuotientFilter
+from .cuckoo import CuckooFilter
 from .hashes import default_fnv_1a, default_md5, default_sha256, fnv_1a, fnv_1a_32, hash_with_depth_bytes, hash_with_depth_int
 
 __version__ = "0.1.0"
@@ -37,6 +39,8 @@ __all__ = [
     "RotatingBloomFilter",
     "QuotientFilter",
     "QuotientFilterError",
+    "CuckooFilter",
+    "CuckooFilterFullError",
     "RotatingBloomFilterError",
     "InitializationError",
     "NotSupportedError",

@@ -78,6 +78,13 @@ PROTOTYPES = {
     "psk_qf_check": (_int, [_u32, _vp, _vp, _vp, _vp, *_KEYS, _int, _vp, _int, _vp]),
     "psk_qf_check_alt": (_int, [_u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _int, _vp]),
     "psk_qf_decode": (_int, [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _int, _vp]),
+    "psk_ck_triples": (_int, [_u64, _u32, *_KEYS, _int, _vp, _int, _vp]),
+    "psk_ck_check": (_int, [_u64, _u32, _u32, _vp, _vp, *_KEYS, _int, _vp, _int, _vp]),
+    "psk_ck_present": (_int, [_u64, _u32, _vp, _vp, _vp, _u64, _vp, _int, _vp]),
+    "psk_ck_place_sweep": (_int, [_u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _int, _vp]),
+    "psk_ck_place_apply": (_int, [_u64, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _int, _vp]),
+    "psk_ck_insert": (_int, [_u64, _u32, _u32, _vp, _vp, _vp, _u64, _u64, _u64, _int, _u64, _vp, _vp, _int, _vp]),
+    "psk_ck_remove": (_int, [_u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _int, _vp]),
     "psk_table_or": (_int, [_vp, _vp, _u64, _int, _vp]),
     "psk_table_and": (_int, [_vp, _vp, _u64, _int, _vp]),
     "psk_table_popcount": (_int, [_vp, _u64, C.POINTER(_u64), _int, _vp]),

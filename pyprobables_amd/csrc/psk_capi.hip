@@ -6,6 +6,7 @@
 #include "psk_window.hpp"
 #include "psk_running.hpp"
 #include "psk_quotient.hpp"
+#include "psk_cuckoo.hpp"
 
 #include <chrono>
 #include <map>
@@ -1982,6 +1983,64 @@ extern "C" int psk_qf_check(uint32_t q, const void *filter_dev, const uint32_t *
         const QfTable t{filter_dev, occupied_dev, continuation_dev, shifted_dev, q};
         PSK_TRY(with_source(b, [&](auto src) {
             hipLaunchKernelGGL((k_qf_check<decltype(src)>), dim3(grid_for_keys(n)), dim3(kBlock), 0, st, src, t, (uint8_t *)o.dev, n);
+            HIP_TRY(hipGetLastError());
+            return (int)PSK_OK;
+        }));
+    }
+    return finish(where, &o, st);
+}
+
+// ------------------------------------------------------------------ cuckoo filter: the calls that take KEYS (psk_cuckoo.hip holds the rest)
+static int ck_geom(uint64_t capacity, uint32_t bucket_size, uint32_t fp_bits, CkGeom *g)
+{
+    if (!ck_make_geom(capacity, bucket_size, fp_bits, g))
+        return fail(PSK_EINVAL, "cuckoo filter: capacity must be in 1 .. 2^31 - 1, bucket_size >= 1, fingerprint bits in 1 .. 32 (got %llu x %u, %u bits)",
+                    (unsigned long long)capacity, bucket_size, fp_bits);
+    return PSK_OK;
+}
+
+// out[3][n] = (fp, idx_1, idx_2) of every key (cuckoo.py:483-506 _indicies_from_fingerprint / _generate_fingerprint_info)
+extern "C" int psk_ck_triples(uint64_t capacity, uint32_t fp_bits, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, int where,
+                              uint32_t *out, int device, void *stream)
+{
+    CkGeom g;
+    PSK_TRY(ck_geom(capacity, 1, fp_bits, &g));
+    if (layout == PSK_KEYS_HASHES && key_len < 1) return fail(PSK_EINVAL, "pre-hashed batch carries no hash per key");
+    if (n && !out) return fail(PSK_EINVAL, "out is NULL");
+    PSK_USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    Batch b;
+    PSK_TRY(stage_batch(g_hkeys, g_hoffs, layout, data, offsets, n, key_len, where, st, &b));
+    OutBuf o;
+    PSK_TRY(stage_out(g_hout, out, n * 12, where, &o));
+    if (n) {
+        PSK_TRY(with_source(b, [&](auto src) {
+            hipLaunchKernelGGL((k_ck_triples<decltype(src)>), dim3(grid_for_keys(n)), dim3(kBlock), 0, st, src, g, (uint32_t *)o.dev, n);
+            HIP_TRY(hipGetLastError());
+            return (int)PSK_OK;
+        }));
+    }
+    return finish(where, &o, st);
+}
+
+// out[i] = check(key_i) (cuckoo.py:306-315): hash, idx_1's row, idx_2's row only if needed, in one kernel
+extern "C" int psk_ck_check(uint64_t capacity, uint32_t bucket_size, uint32_t fp_bits, const uint32_t *buckets_dev, const uint32_t *fill_dev, int layout,
+                            const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, uint8_t *out, int device, void *stream)
+{
+    CkGeom g;
+    PSK_TRY(ck_geom(capacity, bucket_size, fp_bits, &g));
+    if (!buckets_dev || !fill_dev) return fail(PSK_EINVAL, "NULL table pointer");
+    if (layout == PSK_KEYS_HASHES && key_len < 1) return fail(PSK_EINVAL, "pre-hashed batch carries no hash per key");
+    if (n && !out) return fail(PSK_EINVAL, "out is NULL");
+    PSK_USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    Batch b;
+    PSK_TRY(stage_batch(g_hkeys, g_hoffs, layout, data, offsets, n, key_len, where, st, &b));
+    OutBuf o;
+    PSK_TRY(stage_out(g_hout, out, n, where, &o));
+    if (n) {
+        PSK_TRY(with_source(b, [&](auto src) {
+            hipLaunchKernelGGL((k_ck_check<decltype(src)>), dim3(grid_for_keys(n)), dim3(kBlock), 0, st, src, g, buckets_dev, fill_dev, (uint8_t *)o.dev, n);
             HIP_TRY(hipGetLastError());
             return (int)PSK_OK;
         }));

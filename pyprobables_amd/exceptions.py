@@ -40,6 +40,11 @@ class QuotientFilterError(ProbablesBaseException):
     """a QuotientFilter that cannot be built, grown, shrunk or merged (reference exceptions.py QuotientFilterError)"""
 
 
+class CuckooFilterFullError(ProbablesBaseException):
+    """a CuckooFilter that could not place a fingerprint within ``max_swaps`` kicks, or failed to expand (reference exceptions.py
+    CuckooFilterFullError); raised by a batch call it carries ``index``, the position of the key in the batch"""
+
+
 class NativeLibraryError(RuntimeError):
     """libpsk_hip.so (the HIP engine) is missing, failed to load, or reported an error.
 
