@@ -8,7 +8,11 @@ value whose truncated quotient estimate is one short), and restate the three ske
 * CountingBloom    counter ``h % m`` per hash (a repeated index counts twice), saturating at 2^32 - 1;
 * CountMinSketch   bin ``h_i % width + i * width`` per row, saturating at 2^31 - 1; min / mean / mean-min queries.
 
-Only numpy and Python integers: nothing here imports the engine or the oracle, so it can check both.
+The last section does the same for the cuckoo filter's triples: fingerprints at which the decimal digits of ``str(fp)`` or the 32-bit word
+turn over, capacities up to 2^31 - 1 at which the second index needs (or never needs) the correction of its quotient estimate, and the rule
+itself in Python integers.
+
+Only numpy and Python integers: nothing here imports the engine, the oracle or the cuckoo model, so it can check all three.
 """
 
 from __future__ import annotations
@@ -249,3 +253,50 @@ def cms_running(width: int, depth: int, hashes, weights, query: str, bins=None, 
             res = calc[depth // 2] if depth % 2 else (calc[depth // 2] + calc[depth // 2 - 1]) // 2
         out[i] = res
     return out, bins.astype(np.int32), els
+
+
+# ------------------------------------------------------------------ cuckoo filter
+# A key of a cuckoo filter becomes (fp, idx_1, idx_2): fp = h & (2^bits - 1), idx_1 = fp % capacity, idx_2 = fnv_1a(str(fp)) % capacity.
+# The capacities: the smallest ones, a prime, a power of two, and four near 2^31 -- two of them (1_610_612_737 and 2_146_483_645) chosen
+# because a quarter of all 64-bit hashes have a one-short quotient estimate there, which 2^31 - 1 (2^64 mod c = 4) practically never has.
+CK_CAPACITIES = (1, 2, 3, 37, 4096, 1_000_003, 2**30, 1_610_612_737, 2_146_483_645, 2**31 - 1)
+FNV_BASIS, FNV_PRIME = 14695981039346656037, 1099511628211
+
+
+def fnv_1a(data) -> int:
+    """64-bit FNV-1a, seed 0: a str goes in code point by code point, bytes byte by byte"""
+    h = FNV_BASIS
+    for e in (map(ord, data) if isinstance(data, str) else data):
+        h = ((h ^ e) * FNV_PRIME) % U64
+    return h
+
+
+def ck_triples(hashes, capacity: int, bits: int) -> list:
+    """[(fp, idx_1, idx_2)] per 64-bit hash, in Python integers"""
+    capacity, bits = int(capacity), int(bits)
+    assert capacity >= 1 and 1 <= bits <= 32
+    out = []
+    for h in hashes:
+        fp = int(h) & ((1 << bits) - 1)
+        out.append((fp, fp % capacity, fnv_1a(str(fp)) % capacity))
+    return out
+
+
+def ck_edge_fingerprints(seed: int = 0) -> list:
+    """fingerprints at which the decimal digits or the 32-bit word turn over, and seeded random ones of every bit length (4375 in all)"""
+    fps = [0, 1]
+    for k in range(1, 10):
+        fps += [10**k - 1, 10**k]
+    fps += [2**31 - 1, 2**31, 2**32 - 1]
+    rng = np.random.default_rng(seed)
+    for length in range(1, 33):
+        fps += [int(x) for x in rng.integers(1 << (length - 1), 1 << length, size=8, dtype=np.uint64)]
+    fps += [int(x) for x in rng.integers(0, 1 << 32, size=4096, dtype=np.uint64)]
+    assert len(fps) == 4375 and all(0 <= fp < 2**32 for fp in fps)
+    return fps
+
+
+def ck_short(h: int, capacity: int) -> bool:
+    """the truncated quotient estimate of ``h // capacity`` is one short: a reduction by that estimate needs its correction step"""
+    h, capacity = int(h), int(capacity)
+    return (h * (U64 // capacity)) >> 64 == h // capacity - 1

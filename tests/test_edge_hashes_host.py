@@ -1,5 +1,11 @@
 """tests/edge_hashes.py checked on the host: the chosen hashes hit the cells they were built for (Python integers), and the numpy references
-agree with the sequential oracle on pre-hashed streams -- keys whose hashes all name one cell and hash rows with k + 3 columns included."""
+agree with the sequential oracle on pre-hashed streams -- keys whose hashes all name one cell and hash rows with k + 3 columns included.
+The cuckoo filter's triples: ``ck_triples`` is the model's and the reference's rule, its chosen inputs reach both branches of the index
+arithmetic, and each way that arithmetic could be subtly wrong, restated here, gives another answer on them."""
+
+import os
+import sys
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -157,3 +163,102 @@ def test_cms_reference_agrees_with_the_oracle(oracle, width, depth):
         oc.add_alt(h[0], wi)
         ref.add(idx[:1], wi)
         assert np.array_equal(ref.table(np.int32), oc.bins) and ref.els == oc.els_added
+
+
+# ------------------------------------------------------------------ cuckoo filter
+CK_FPS = E.ck_edge_fingerprints(0)
+CK_CORRECTED = (3, 37, 1_000_003, 1_610_612_737, 2_146_483_645)
+CK_REF = Path(os.environ.get("PYPROBABLES_REFERENCE", "/root/reference"))
+
+
+def test_ck_edge_fingerprints_hold_what_they_promise():
+    got = set(CK_FPS)
+    assert {0, 1, 2**31 - 1, 2**31, 2**32 - 1} <= got and all({10**k - 1, 10**k} <= got for k in range(1, 10))
+    assert all(sum(fp.bit_length() == n for fp in CK_FPS) >= 8 for n in range(1, 33))
+    assert CK_FPS == E.ck_edge_fingerprints(0) != E.ck_edge_fingerprints(1)
+    assert E.CK_CAPACITIES == (1, 2, 3, 37, 4096, 1_000_003, 2**30, 1_610_612_737, 2_146_483_645, 2**31 - 1)
+    assert E.fnv_1a("") == E.FNV_BASIS and E.fnv_1a(b"a") == E.fnv_1a("a") == 0xAF63DC4C8601EC8C  # (the published test vector)
+
+
+@pytest.mark.parametrize("bits", [1, 4, 8, 13, 21, 29, 32])
+@pytest.mark.parametrize("cap", [1, 3, 37, 4096, 1_000_003, 2_146_483_645, 2**31 - 1])
+def test_ck_triples_equal_the_model(cap, bits):
+    import cuckoo_model as M
+
+    m = M.CuckooModel.__new__(M.CuckooModel)  # (no table of `cap` rows: only the two functions of capacity and width)
+    m.capacity, m.finger_bits = cap, bits
+    hashes = [fp | (i * 0x9E3779B97F4A7C15 % U64 & ~0xFFFFFFFF) for i, fp in enumerate(CK_FPS[:600])]  # noise above the fingerprint
+    assert E.ck_triples(hashes, cap, bits) == [(fp := h & ((1 << bits) - 1), *m.indices(fp)) for h in hashes]
+    keys = [f"k{i}" for i in range(50)] + ["é€", b"\x00\xff", ""]
+    assert E.ck_triples([E.fnv_1a(k) for k in keys], cap, bits) == [(m.fingerprint(k), *m.indices(m.fingerprint(k))) for k in keys]
+    assert [E.fnv_1a(k) for k in keys] == [M.fnv_1a(k) for k in keys]
+
+
+def test_ck_triples_equal_the_live_reference():
+    if not (CK_REF / "probables").is_dir():
+        pytest.skip("the reference checkout is not on this machine")
+    sys.path.insert(0, str(CK_REF))
+    try:
+        from probables import CuckooFilter
+    finally:
+        sys.path.remove(str(CK_REF))
+    keys = [f"k{i}" for i in range(200)] + ["é€", ""]
+    for rate, B, bits in ((0.5, 4, 4), (0.01, 4, 10), (0.001, 5, 14), (1e-5, 7, 21), (1e-6, 16, 25), (1e-7, 16, 29), (1e-8, 16, 32)):
+        for cap in (3, 37, 1_000_003, 2_146_483_645, 2**31 - 1):
+            ref = CuckooFilter.init_error_rate(rate, capacity=5, bucket_size=B)
+            assert ref.fingerprint_size_bits == bits
+            ref._cuckoo_capacity = cap  # (the two functions under test read nothing else; a table of 2^31 rows is not built)
+            assert [ref._generate_fingerprint_info(k) for k in keys] == [(i1, i2, fp) for fp, i1, i2 in E.ck_triples(map(E.fnv_1a, keys), cap, bits)]
+            some = [fp for fp in CK_FPS[:300] if fp < 1 << bits]
+            assert [ref._indicies_from_fingerprint(fp) for fp in some] == [t[1:] for t in E.ck_triples(some, cap, 32)]
+
+
+@pytest.mark.parametrize("cap", CK_CORRECTED)
+def test_ck_fingerprints_reach_both_branches_of_the_correction(cap):
+    short = sum(E.ck_short(E.fnv_1a(str(fp)), cap) for fp in CK_FPS)
+    print(cap, short, len(CK_FPS) - short)
+    assert short >= 100 and len(CK_FPS) - short >= 100
+    # (2^31 - 1 leaves 2^64 mod c = 4: next to no hash is short there, which is why the two capacities above stand next to it)
+    assert sum(E.ck_short(E.fnv_1a(str(fp)), 2**31 - 1) for fp in CK_FPS) < 100
+
+
+def _decimal_hash(fp, places=10, keep_last_zero=True):
+    """fnv_1a(str(fp)) as a digit loop from the most significant of `places` places, leading zeros suppressed"""
+    h, started, p = E.FNV_BASIS, False, 10 ** (places - 1)
+    for k in range(places):
+        digit = fp // p
+        fp -= digit * p
+        started = started or digit != 0 or (keep_last_zero and k == places - 1)
+        if started:
+            h = ((h ^ (0x30 + digit)) * E.FNV_PRIME) % U64
+        p //= 10
+    return h
+
+
+def test_ck_inputs_tell_the_wrong_variants_apart():
+    """each way the triples could be subtly wrong, restated here: on the chosen inputs its output differs from ck_triples"""
+    assert [_decimal_hash(fp) for fp in CK_FPS] == [E.fnv_1a(str(fp)) for fp in CK_FPS]  # (the loop written right IS str())
+    for cap in CK_CORRECTED:
+        want = [t[2] for t in E.ck_triples(CK_FPS, cap, 32)]
+        magic = U64 // cap
+        uncorrected = [(h := E.fnv_1a(str(fp))) - ((h * magic) >> 64) * cap for fp in CK_FPS]
+        wrong = [fp for fp, a, b in zip(CK_FPS, uncorrected, want) if a != b]
+        assert len(wrong) >= 100 and all(E.ck_short(E.fnv_1a(str(fp)), cap) for fp in wrong), "the estimate without its correction"
+    for cap in E.CK_CAPACITIES[1:]:
+        want = {fp: t[2] for fp, t in zip(CK_FPS, E.ck_triples(CK_FPS, cap, 32))}
+        if cap >= 37:  # (modulo 2 and 3 the empty string and "0" happen to agree)
+            assert _decimal_hash(0, keep_last_zero=False) % cap != want[0], "fp == 0 hashed as the empty string"
+        big = [fp for fp in CK_FPS if fp >= 10**9]
+        assert len(big) > 1000 and 10**9 in big and 2**32 - 1 in big
+        assert sum(_decimal_hash(fp, places=9) % cap != want[fp] for fp in big) >= 1000, "a digit loop of 9 places"
+    # the mask: bits rounded up to whole bytes, and idx_2 from the hash before the mask
+    rng = np.random.default_rng(8)
+    hashes = [int(h) for h in rng.integers(0, 2**64, size=200, dtype=np.uint64)] + [U64 - 1, 1 << 63]
+    for bits in range(1, 33):
+        want = E.ck_triples(hashes, 1_000_003, bits)
+        if bits % 8:
+            assert E.ck_triples(hashes, 1_000_003, (bits + 7) // 8 * 8) != want and want[-2][0] == (1 << bits) - 1, "a byte mask for a bit mask"
+        if bits < 32:
+            unmasked = [(fp, i1, E.fnv_1a(str(h & 0xFFFFFFFF)) % 1_000_003) for h, (fp, i1, _) in zip(hashes, want)]
+            assert sum(a != b for a, b in zip(unmasked, want)) >= 100, "idx_2 from the unmasked hash"
+        assert want[-1] == (0, 0, E.fnv_1a("0") % 1_000_003)  # 2^63: nothing of it is left

@@ -3,7 +3,6 @@
 too small for against tests/cuckoo_model.py (which tests/test_cuckoo_model.py ties to the reference).  All comparisons are exact."""
 
 import hashlib
-import itertools
 import json
 import random
 import struct
@@ -19,11 +18,11 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tests"))
 
 import cuckoo_model as M  # noqa: E402
+from cuckoo_recipe import POLICIES, assert_same, jacobi, model_of, run_class  # noqa: E402
 
 FIXTURE = json.loads((ROOT / "tests" / "golden" / "golden_cuckoo.json").read_text())
 CASES = FIXTURE["cases"]
 IDS = [c["name"] for c in CASES]
-POLICIES = ["auto", "parallel", "sequential"]
 
 
 @pytest.fixture(scope="module")
@@ -47,34 +46,6 @@ def case_keys(case):
 
 def case_ops(case):
     return [(o[0], int(o[1:])) for o in case["ops"].split(",")]
-
-
-def run_class(pa, params, keys, ops, seed, policy):
-    """the op stream in batches cut where add turns into remove -> (filter, remove returns, error index, error message)"""
-    random.seed(seed)
-    p = dict(params)
-    cf = pa.CuckooFilter(**p)
-    cf._insert_policy = policy
-    rets, at = [], 0
-    for op, group in itertools.groupby(ops, key=lambda o: o[0]):
-        batch = [keys[k] for _, k in group]
-        if op == "a":
-            try:
-                cf.add_many(batch)
-            except pa.CuckooFilterFullError as ex:
-                return cf, rets, at + ex.index, str(ex)
-        else:
-            rets += [int(r) for r in cf.remove_many(batch)]
-        at += len(batch)
-    return cf, rets, None, None
-
-
-def model_of(params, seed=None, state=None):
-    if state is None:
-        random.seed(seed)
-        state = random.getstate()
-    return M.CuckooModel(params["capacity"], params["bucket_size"], params["max_swaps"], params["expansion_rate"], params["auto_expand"],
-                         params["finger_size"] * 8, M.MT19937(state))
 
 
 @pytest.mark.parametrize("policy", POLICIES)
@@ -101,13 +72,6 @@ def test_reference_known_answer(pa):
     assert all(cf.check_many([str(i) for i in range(1000)])) and "5" in cf and "-5" not in cf
 
 
-def assert_same(cf, m):
-    assert bytes(cf) == m.export()
-    assert (cf.elements_added, cf.capacity) == (m.elements_added, m.capacity)
-    assert random.getstate() == m.rng.getstate()
-    assert cf.buckets == m.buckets
-
-
 @pytest.mark.parametrize("policy", POLICIES)
 @pytest.mark.parametrize("cap,B", [(5, 1), (5, 3), (13, 1), (13, 3)])
 def test_tiny_capacities_against_the_model(pa, cap, B, policy):
@@ -121,27 +85,6 @@ def test_tiny_capacities_against_the_model(pa, cap, B, policy):
     assert err_at is None
     assert_same(cf, m)
     assert cf.check_many(keys).tolist() == [m.check(k) for k in keys]
-
-
-def jacobi(triples, B, max_sweeps=32):
-    """the placement's iteration on an empty table, written out sequentially: every sweep decides each key from the PREVIOUS sweep's
-    decisions of the keys in front of it; it stops at a fixed point or once the first K lies in front of the first change
-    -> (sweeps, accepted prefix = min(first change of the last sweep, first K))"""
-    m = len(triples)
-    d = [1] * m
-    for sweeps in range(1, max_sweeps + 1):
-        held, new = {}, []
-        for j, (_, i1, i2) in enumerate(triples):
-            new.append(1 if held.get(i1, 0) < B else 2 if held.get(i2, 0) < B else 3)
-            if d[j] != 3:
-                b = (i1, i2)[d[j] - 1]
-                held[b] = held.get(b, 0) + 1
-        changed = next((j for j in range(m) if new[j] != d[j]), m + 1)
-        kick = next((j for j in range(m) if new[j] == 3), m + 1)
-        d = new
-        if changed > m or kick < changed:
-            break
-    return sweeps, min(m, changed, kick)
 
 
 @pytest.fixture(scope="module")
