@@ -21,7 +21,7 @@
 // idx_1's row left to right, then idx_2's row (cuckoo.py:317-330, list.remove takes the first occurrence), one per request: the t-th
 // request for a fingerprint (t from 0, the host ranks them) succeeds iff t < copies and takes copy number t.  Lanes mark slots in a
 // per-row bit mask; the lane that swaps a non-zero mask out compacts that row to the left, zeroes what it vacates and lowers `fill`.
-#include "psk_host.hpp"
+#include "psk_stage.hpp"
 #include "psk_cuckoo.hpp"
 
 namespace {
@@ -296,12 +296,15 @@ __global__ __launch_bounds__(kBlock) void k_ck_rm_compact(CkGeom g, CkTable t, c
     }
 }
 
-int geom_of(uint64_t capacity, uint32_t bucket_size, CkGeom *g)
+int ck_geom(uint64_t capacity, uint32_t bucket_size, uint32_t fp_bits, CkGeom *g)
 {
-    if (!ck_make_geom(capacity, bucket_size, 32, g))
-        return fail(PSK_EINVAL, "cuckoo filter: capacity must be in 1 .. 2^31 - 1 and bucket_size >= 1 (got %llu x %u)", (unsigned long long)capacity, bucket_size);
+    if (!ck_make_geom(capacity, bucket_size, fp_bits, g))
+        return fail(PSK_EINVAL, "cuckoo filter: capacity must be in 1 .. 2^31 - 1, bucket_size >= 1, fingerprint bits in 1 .. 32 (got %llu x %u, %u bits)",
+                    (unsigned long long)capacity, bucket_size, fp_bits);
     return PSK_OK;
 }
+// (the calls that take triples: the fingerprints are whole 32-bit words by then)
+int geom_of(uint64_t capacity, uint32_t bucket_size, CkGeom *g) { return ck_geom(capacity, bucket_size, 32, g); }
 
 }  // namespace
 
@@ -385,4 +388,31 @@ extern "C" int psk_ck_remove(uint64_t capacity, uint32_t bucket_size, uint32_t *
     hipLaunchKernelGGL(k_ck_rm_compact, dim3(grid_for_keys(n)), dim3(kBlock), 0, st, g, t, triples_dev, n, row_marks_dev);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
+}
+
+// out[3][n] = (fp, idx_1, idx_2) of every key (cuckoo.py:483-506 _indicies_from_fingerprint / _generate_fingerprint_info)
+extern "C" int psk_ck_triples(uint64_t capacity, uint32_t fp_bits, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, int where,
+                              uint32_t *out, int device, void *stream)
+{
+    CkGeom g;
+    PSK_TRY(ck_geom(capacity, 1, fp_bits, &g));
+    if (layout == PSK_KEYS_HASHES && key_len < 1) return fail(PSK_EINVAL, "pre-hashed batch carries no hash per key");
+    if (n && !out) return fail(PSK_EINVAL, "out is NULL");
+    return keyed_call(layout, data, offsets, n, key_len, where, out, n * 12, device, stream, [&](auto src, void *out_dev, hipStream_t st) {
+        hipLaunchKernelGGL((k_ck_triples<decltype(src)>), dim3(grid_for_keys(n)), dim3(kBlock), 0, st, src, g, (uint32_t *)out_dev, n);
+    });
+}
+
+// out[i] = check(key_i) (cuckoo.py:306-315): hash, idx_1's row, idx_2's row only if needed, in one kernel
+extern "C" int psk_ck_check(uint64_t capacity, uint32_t bucket_size, uint32_t fp_bits, const uint32_t *buckets_dev, const uint32_t *fill_dev, int layout,
+                            const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, uint8_t *out, int device, void *stream)
+{
+    CkGeom g;
+    PSK_TRY(ck_geom(capacity, bucket_size, fp_bits, &g));
+    if (!buckets_dev || !fill_dev) return fail(PSK_EINVAL, "NULL table pointer");
+    if (layout == PSK_KEYS_HASHES && key_len < 1) return fail(PSK_EINVAL, "pre-hashed batch carries no hash per key");
+    if (n && !out) return fail(PSK_EINVAL, "out is NULL");
+    return keyed_call(layout, data, offsets, n, key_len, where, out, n, device, stream, [&](auto src, void *out_dev, hipStream_t st) {
+        hipLaunchKernelGGL((k_ck_check<decltype(src)>), dim3(grid_for_keys(n)), dim3(kBlock), 0, st, src, g, buckets_dev, fill_dev, (uint8_t *)out_dev, n);
+    });
 }

@@ -1,6 +1,6 @@
 // psk_host.hpp -- host-side declarations shared by the translation units of libpsk_hip.so
-// (psk_capi.hip = C ABI + direct kernels; psk_part_*.hip = the partitioned-path launchers, split so that
-// hipcc can build the ~300 k_part_scatter instantiations in parallel).
+// (psk_capi.hip and one unit per sketch = C ABI + direct kernels, over the staging layer of psk_stage.hpp; psk_part_*.hip = the
+// partitioned-path launchers, split so that hipcc can build the ~300 k_part_scatter instantiations in parallel).
 #pragma once
 #include "psk_device.hpp"
 #include "psk_partition.hpp"
@@ -105,7 +105,7 @@ struct psk_sketch {
     uint64_t padded_bytes, logical_bytes;
     long long *ctr;    // device int64[PSK_CTR_COUNT]
     DevBuf s_keys, s_offs, s_w, s_out, s_aux;  // staging for PSK_HOST buffers
-    volatile uint32_t *mbox = nullptr;         // completion mailbox of tiny PSK_HOST batches (psk_capi.hip Mailbox): a pinned word the
+    volatile uint32_t *mbox = nullptr;         // completion mailbox of tiny PSK_HOST batches (psk_stage.hpp Mailbox): a pinned word the
     uint32_t mbox_seq = 0;                     // kernel stores the call's sequence number into, behind its results
     uint32_t mbox_timeouts = 0, mbox_skipped = 0;  // polls in a row that gave up / calls since the handle stopped polling (mailbox_arm)
     DevBuf s_part, s_cnt;                      // partitioned path: bucket buffer + per-bucket fill counts
@@ -119,7 +119,7 @@ struct psk_sketch {
     DevBuf s_tally;                            // weighted pass 1: (sum w, sum |w|) per workgroup, folded by k_tally_fold
     DevBuf s_brw;                              // borrowed write-combined batches: pointer / prefix tables of a flush
     DevBuf s_vals, s_perm, s_run;              // partitioned counter lookups: values, per-key stage positions, per-(tile, slice) runs
-    // Weighted counter updates: the caller (psk_capi.hip) posts what has to be accounted for the batch; a partitioned launcher
+    // Weighted counter updates: the caller (post_acct, psk_stage.hpp) posts what has to be accounted for the batch; a partitioned launcher
     // that scatters the weights takes the request over (PayWeight::tally sums them inside pass 1) and clears `pending`;
     // otherwise the caller runs the stand-alone pass over the weights (k_weight_sum).
     struct {
@@ -798,7 +798,8 @@ PSK_DECLARE_VARIANTS(int, cbf_check_partitioned, (psk_sketch *s, const Batch &b,
 // s_part / s_cnt; an overflowing segment raises *flag): shared by the Bloom return trip and the CountingBloomFilter's 4-bit-slice lookups --
 // ONE set of instantiations (psk_part_cbf_check.hip) instead of one per caller.  *fits = false: a tile too large for 16-bit stage positions.
 PSK_DECLARE_VARIANTS(int, bloomidx_lookup_scatter, (psk_sketch *s, const Batch &sub, uint64_t cnt, uint32_t kk, PartGeom *g, uint32_t *flag, hipStream_t st, bool *handled, bool *fits))
-PSK_HIDDEN int flush_combined(psk_sketch *s, hipStream_t st);  // apply the write-combined CBF updates, if any (psk_capi.hip)
+PSK_HIDDEN int flush_combined(psk_sketch *s, hipStream_t st);  // apply the write-combined CBF updates, if any (psk_cbf.hip)
+PSK_HIDDEN int drop_pending(psk_sketch *s, hipStream_t st);    // ... or forget them: the table is cleared or replaced (psk_cbf.hip)
 PSK_HIDDEN int clear_materialize(psk_sketch *s, hipStream_t st);  // run the deferred clear of a Bloom table now, if one is pending (psk_capi.hip)
 // pass 1 of a unit-weight CBF batch, appended to the handle's persistent add (neg = 0) / decrement (neg = 1) list; *done = false:
 // the batch / table is not eligible (nothing was launched)

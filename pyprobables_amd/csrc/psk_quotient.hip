@@ -17,7 +17,7 @@
 // slot x with continuation = shifted = 0: an empty slot (the next run behind it belongs to the next occupied quotient) or a cluster start
 // (its run is its own quotient's).  Such a slot exists in every table, the full one included (the element with the largest q_j - j sits
 // in its own slot), so a full table decodes like any other.
-#include "psk_host.hpp"
+#include "psk_stage.hpp"
 #include "psk_quotient.hpp"
 
 namespace {
@@ -287,4 +287,30 @@ extern "C" int psk_qf_decode(uint32_t q, const void *filter_dev, const uint32_t 
         hipLaunchKernelGGL((k_qf_decode_emit<uint32_t>), dim3(grid), dim3(kBlock), 0, st, (const uint32_t *)filter_dev, occupied_dev, continuation_dev, shifted_dev, q, nwords, valid, counts, marks_dev, out_dev, out_cap);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
+}
+
+// out[i] = fnv_1a_32(key_i, 0)  (hashes.py:106-122; quotientfilter.py:151 add, :194 check); PSK_KEYS_HASHES: the low half of each row's first hash
+extern "C" int psk_qf_hash(int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, uint32_t *out, int device,
+                           void *stream)
+{
+    if (layout == PSK_KEYS_HASHES && key_len < 1) return fail(PSK_EINVAL, "pre-hashed batch carries no hash per key");
+    if (n && !out) return fail(PSK_EINVAL, "out is NULL");
+    return keyed_call(layout, data, offsets, n, key_len, where, out, n * 4, device, stream, [&](auto src, void *out_dev, hipStream_t st) {
+        hipLaunchKernelGGL((k_qf_hash<decltype(src)>), dim3(grid_for_keys(n)), dim3(kBlock), 0, st, src, (uint32_t *)out_dev, n);
+    });
+}
+
+// out[i] = key_i's hash is in the table (quotientfilter.py:187-206 check / check_alt): hash and walk in one kernel
+extern "C" int psk_qf_check(uint32_t q, const void *filter_dev, const uint32_t *occupied_dev, const uint32_t *continuation_dev, const uint32_t *shifted_dev,
+                            int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, uint8_t *out, int device,
+                            void *stream)
+{
+    PSK_TRY(check_q(q));
+    if (!filter_dev || !occupied_dev || !continuation_dev || !shifted_dev) return fail(PSK_EINVAL, "NULL table pointer");
+    if (layout == PSK_KEYS_HASHES && key_len < 1) return fail(PSK_EINVAL, "pre-hashed batch carries no hash per key");
+    if (n && !out) return fail(PSK_EINVAL, "out is NULL");
+    const psk::QfTable t{filter_dev, occupied_dev, continuation_dev, shifted_dev, q};
+    return keyed_call(layout, data, offsets, n, key_len, where, out, n, device, stream, [&](auto src, void *out_dev, hipStream_t st) {
+        hipLaunchKernelGGL((k_qf_check<decltype(src)>), dim3(grid_for_keys(n)), dim3(kBlock), 0, st, src, t, (uint8_t *)out_dev, n);
+    });
 }
