@@ -227,7 +227,13 @@ def cms_query(vals, query: str, width: int, els_added: int) -> np.ndarray:
 
 def cms_running(width: int, depth: int, hashes, weights, query: str, bins=None, els: int = 0):
     """the ordered add as a sequential loop in Python integers: (int64 results[n], int32 bins, elements_added)"""
+    return cms_running_counted(width, depth, hashes, weights, query, bins, els)[:3]
+
+
+def cms_running_counted(width: int, depth: int, hashes, weights, query: str, bins=None, els: int = 0):
+    """``cms_running`` and, as a fourth value, its clamp count: the (op, row) pairs with ``bin + w > INT32_MAX``"""
     width, depth = int(width), int(depth)
+    clamps = 0
     idx = cms_indices(hashes, width, depth).tolist()
     bins = np.zeros(width * depth, dtype=np.int64) if bins is None else np.asarray(bins).astype(np.int64)
     n = len(idx)
@@ -236,7 +242,9 @@ def cms_running(width: int, depth: int, hashes, weights, query: str, bins=None, 
     for i, row in enumerate(idx):
         vals = []
         for x in row:  # (an index cannot repeat inside one key: the rows are disjoint)
-            v = min(int(bins[x]) + w[i], I32_MAX)
+            v = int(bins[x]) + w[i]
+            if v > I32_MAX:
+                v, clamps = I32_MAX, clamps + 1
             bins[x] = v
             vals.append(v)
         els = min(els + w[i], I64_MAX)
@@ -252,7 +260,92 @@ def cms_running(width: int, depth: int, hashes, weights, query: str, bins=None, 
             calc = sorted(v - (els - v) // (width - 1) for v in vals)
             res = calc[depth // 2] if depth % 2 else (calc[depth // 2] + calc[depth // 2 - 1]) // 2
         out[i] = res
-    return out, bins.astype(np.int32), els
+    return out, bins.astype(np.int32), els, clamps
+
+
+def cms_running_vec(width: int, depth: int, hashes, weights, query, bins=None, els: int = 0):
+    """the same rule in numpy, for batches the loop is too slow for: (int64 results[n], {bin index: value} of the touched bins,
+    elements_added, clamp count).  ``query``: one name, or a tuple of names (the results are a tuple then: the rows are walked once).
+    ``bins``: None (an empty table), one int (every bin holds it) or the whole table (read at the touched bins only); nothing of the
+    table's size is allocated here.
+
+    Weights are >= 0, so a bin never decreases and clamping at every step equals clamping the exact running sum once: per row a stable
+    argsort of the bins, the cumulative sum of the weights inside each run of equal bins (int64: n * INT32_MAX < 2^63), the bin's start
+    value on top, the clamp, and back to op order.  An op clamps when the (clamped) value in front of it plus its weight passes INT32_MAX."""
+    width, depth, els = int(width), int(depth), int(els)
+    h = np.asarray(hashes, dtype=np.uint64)
+    n = h.shape[0]
+    assert h.ndim == 2 and h.shape[1] >= depth and n * I32_MAX < I64_MAX
+    w = np.ascontiguousarray(np.broadcast_to(np.asarray(1 if weights is None else weights, dtype=np.int64), (n,)))
+    assert n == 0 or (0 <= int(w.min()) and int(w.max()) <= I32_MAX)
+    vals = np.empty((depth, n), dtype=np.int64)
+    touched, clamps = {}, 0
+    at = np.arange(n, dtype=np.int64)
+    for s in range(depth):
+        col = h[:, s] % np.uint64(width)
+        order = np.argsort(col.astype(np.uint16 if width <= 1 << 16 else np.int64), kind="stable")  # (16-bit keys: numpy's radix sort)
+        sc, sw = col.astype(np.int64)[order], w[order]
+        head = np.ones(n, dtype=bool)
+        head[1:] = sc[1:] != sc[:-1]
+        cs = np.cumsum(sw)
+        first = np.maximum.accumulate(np.where(head, at, 0))  # where this element's run begins
+        seg = cs - (cs - sw)[first]                            # inclusive sum inside the run
+        if bins is None or isinstance(bins, (int, np.integer)):
+            t0 = np.full(n, 0 if bins is None else int(bins), dtype=np.int64)
+        else:
+            t0 = np.asarray(bins)[sc + s * width].astype(np.int64)
+        after = np.minimum(t0 + seg, I32_MAX)
+        clamps += int((np.minimum(t0 + seg - sw, I32_MAX) + sw > I32_MAX).sum())
+        vals[s, order] = after
+        last = np.ones(n, dtype=bool)
+        last[:-1] = head[1:]
+        touched.update(zip((sc[last] + s * width).tolist(), after[last].tolist()))
+    cw = np.cumsum(w)
+    room = I64_MAX - els  # what elements_added can still take (els <= INT64_MAX, so room >= 0; beyond int64 for a negative start: no clamp)
+    els_after = els + np.minimum(cw, min(room, I64_MAX))
+    names = (query,) if isinstance(query, str) else tuple(query)
+    assert all(q in ("min", "mean", "mean-min") for q in names)
+    outs = [np.empty(n, dtype=np.int64) for _ in names]
+    for lo in range(0, n, 1 << 15):  # (the sort of depth values per op, a slab of ops at a time)
+        v = np.sort(vals[:, lo:lo + (1 << 15)].T, axis=1)
+        for q, out in zip(names, outs):
+            if q == "min":
+                res = v[:, 0]
+            elif q == "mean":
+                res = v.sum(axis=1) // depth
+            else:
+                e = els_after[lo:lo + (1 << 15), None]
+                assert int(e.max()) - int(v.min()) <= I64_MAX, "elements_added - bin leaves int64: outside what the sketch claims"
+                calc = np.sort(v - (e - v) // (width - 1), axis=1)
+                res = calc[:, depth // 2] if depth % 2 else (calc[:, depth // 2] + calc[:, depth // 2 - 1]) // 2
+                res = np.where((v[:, 0] == 0) & (v[:, -1] == 0), 0, res)
+            out[lo:lo + (1 << 15)] = res
+    return outs[0] if isinstance(query, str) else tuple(outs), touched, (int(els_after[-1]) if n else els), clamps
+
+
+RUN_DIGIT_EDGES = (0, 1, 255, 256, 257, 65535, 65536, 2**24 - 1, 2**24)
+
+
+def running_digit_columns(width: int, n: int, seed: int = 0) -> np.ndarray:
+    """int64[n] columns of a table ``width`` wide for the ordered add's 8-bit radix sort, interleaved in arrival order: the members of
+    ``RUN_DIGIT_EDGES`` and ``width - 1`` that lie below the width, for every digit position the width has several pairs of columns that
+    differ in exactly that digit (both orders of arrival), and seeded random columns for the rest; every chosen column comes several times,
+    so that its bin is a segment of ops from all over the batch"""
+    width = int(width)
+    rng = np.random.default_rng(seed)
+    chosen = [c for c in (*RUN_DIGIT_EDGES, width - 1) if 0 <= c < width]
+    ndigits = max(1, ((width - 1).bit_length() + 7) // 8)
+    for d in range(ndigits):
+        for _ in range(8):
+            a = int(rng.integers(0, width))
+            b = a ^ (int(rng.integers(1, 256)) << (8 * d))
+            if b < width:  # (the top digit of a narrow table has few values: such a pair may not exist)
+                chosen += [a, b] if rng.integers(0, 2) else [b, a]
+    cols = rng.integers(0, width, size=n, dtype=np.int64)
+    reps = max(1, min(6, (n // 2) // len(chosen)))
+    spots = rng.permutation(n)[: reps * len(chosen)]
+    cols[spots] = np.resize(np.array(chosen, dtype=np.int64), spots.size)
+    return cols
 
 
 # ------------------------------------------------------------------ cuckoo filter

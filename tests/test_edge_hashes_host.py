@@ -165,6 +165,77 @@ def test_cms_reference_agrees_with_the_oracle(oracle, width, depth):
         assert np.array_equal(ref.table(np.int32), oc.bins) and ref.els == oc.els_added
 
 
+@pytest.mark.parametrize("query", ("min", "mean", "mean-min"))
+@pytest.mark.parametrize("width,depth", [(7, 3), (3, 4), (777, 5), (300, 8)])
+def test_vectorised_running_reference_is_the_loop(width, depth, query):
+    """results, touched bins (and nothing else changed), elements_added and clamp count of ``cms_running_vec`` against the Python-integer
+    loop: preloaded negative and at-rail bins, weights of 0 and of INT32_MAX, elements_added starting 10 under INT64_MAX"""
+    rng = np.random.default_rng(width + depth)
+    n = 1500
+    cols = rng.integers(0, width, size=(n, depth))
+    cols[::2, 0] = width - 1  # one long segment
+    h = E.lift(cols, width, 3)
+    pre = rng.integers(0, 50, size=width * depth).astype(np.int32)
+    pre[0::5], pre[1::5], pre[2::5] = E.I32_MAX, -(2**31), E.I32_MAX - 20
+    pre[3::5] = -7
+    weights = {
+        "small": rng.choice([0, 1, 2, 9], size=n),
+        "rail": rng.choice([0, 1, E.I32_MAX, E.I32_MAX - 1, 12345], size=n),
+        "ones": None,
+    }
+    # (elements_added - bin must stay inside int64 for mean-min: the high start goes with an empty or non-negative table)
+    pos = np.where(pre < 0, 3, pre)
+    starts = [(None, 0), (pre, 5), (pos, E.I64_MAX - 10), (None, E.I64_MAX - 10), (pos, E.I64_MAX)]
+    if query != "mean-min":
+        starts.append((pre, E.I64_MAX - 10))
+    for name, w in weights.items():
+        for bins, els in starts:
+            want, wbins, wels, wclamps = E.cms_running_counted(width, depth, h, w, query, bins, els)
+            got, touched, gels, gclamps = E.cms_running_vec(width, depth, h, w, query, bins, els)
+            assert np.array_equal(got, want) and got.dtype == np.int64, (name, els)
+            after = np.zeros(width * depth, dtype=np.int64) if bins is None else bins.astype(np.int64)
+            assert set(touched) == set(np.unique(E.cms_indices(h, width, depth)).tolist())
+            after[list(touched)] = list(touched.values())
+            assert np.array_equal(after, wbins), (name, els)
+            assert (gels, gclamps) == (wels, wclamps), (name, els)
+            assert E.cms_running(width, depth, h, w, query, bins, els)[2] == wels  # (the three-value form is unchanged)
+    assert E.cms_running_counted(width, depth, h, weights["rail"], query, pre, 5)[3] > 0
+    # a uniform preload given as one integer, and the empty batch
+    want = E.cms_running_counted(width, depth, h, weights["small"], query, np.full(width * depth, E.I32_MAX - 500, dtype=np.int32), 9)
+    got = E.cms_running_vec(width, depth, h, weights["small"], query, E.I32_MAX - 500, 9)
+    assert np.array_equal(got[0], want[0]) and got[2:] == want[2:] and all(want[1][k] == v for k, v in got[1].items())
+    assert E.cms_running_vec(width, depth, h[:0], None, query, None, 77)[1:] == ({}, 77, 0)
+    # several queries in one walk of the rows
+    both = E.cms_running_vec(width, depth, h, weights["small"], ("min", query), pre, 5)
+    one = E.cms_running_vec(width, depth, h, weights["small"], query, pre, 5)
+    assert isinstance(both[0], tuple) and np.array_equal(both[0][1], one[0]) and both[1:] == one[1:]
+    assert np.array_equal(both[0][0], E.cms_running(width, depth, h, weights["small"], "min", pre, 5)[0])
+
+
+@pytest.mark.parametrize("width", (1, 2, 255, 256, 257, 65536, 65537, 2**24, 2**24 + 1, 2**28 + 3))
+def test_running_digit_columns(width):
+    n = 5000
+    cols = E.running_digit_columns(width, n, 1)
+    assert cols.shape == (n,) and cols.dtype == np.int64 and 0 <= cols.min() and cols.max() < width
+    got = set(cols.tolist())
+    assert {c for c in (*E.RUN_DIGIT_EDGES, width - 1) if c < width} <= got
+    ndigits = max(1, ((width - 1).bit_length() + 7) // 8)
+    assert ndigits == {1: 1, 2: 1, 255: 1, 256: 1, 257: 2, 65536: 2, 65537: 3, 2**24: 3, 2**24 + 1: 4, 2**28 + 3: 4}[width]
+    if width > 1:
+        u = np.array(sorted(got), dtype=np.int64)
+        x = u[:, None] ^ u[None, :] if u.size <= 600 else None
+        for d in range(ndigits):  # a pair of columns that differ in digit d alone
+            if x is not None:
+                assert ((x != 0) & ((x & ~(0xFF << (8 * d))) == 0)).any(), d
+            else:
+                rest = u & ~np.int64(0xFF << (8 * d))
+                assert (np.unique(rest, return_counts=True)[1] > 1).any(), d
+    # interleaved: a chosen column's ops are spread over the three sort tiles of the batch
+    if width > 600:
+        where = np.flatnonzero(cols == width - 1)
+        assert where.size >= 2 and np.unique(cols).size > 1000
+
+
 # ------------------------------------------------------------------ cuckoo filter
 CK_FPS = E.ck_edge_fingerprints(0)
 CK_CORRECTED = (3, 37, 1_000_003, 1_610_612_737, 2_146_483_645)
