@@ -389,6 +389,43 @@ int psk_ck_insert(uint64_t capacity, uint32_t bucket_size, uint32_t max_swaps, u
 int psk_ck_remove(uint64_t capacity, uint32_t bucket_size, uint32_t *buckets_dev, uint32_t *fill_dev, const uint32_t *triples_dev,
                   const uint32_t *rank_dev, uint64_t n, uint32_t *row_marks_dev, uint8_t *out_dev, int device, void *stream);
 
+/* ------------------------------------------------------------ CountingCuckooFilter
+ * cuckoo/countingcuckoo.py: the cuckoo filter as a multiset.  No handle: the caller owns (device memory)
+ *   bins      uint32[capacity][bucket_size][2], (fingerprint, count) pairs, every row filled from the left, its unused pairs 0: the
+ *             reference's export byte for byte (an export is this array plus the "II" footer)
+ *   fill      uint32[capacity], the bins in each row
+ * Limits, triples and the MT19937 words as for the CuckooFilter; psk_ck_triples and psk_ck_place_sweep (which reads only `fill`) serve both.
+ *   check        out[i] = check(key_i) (countingcuckoo.py:175-191): the count of the first bin that holds the fingerprint, idx_1's row
+ *                left to right, else idx_2's, else 0; hash and lookup in one kernel, `where` as everywhere
+ *   present      0 / 1 per device triple
+ *   place_apply  psk_ck_place_apply for this layout: key j is written as (fp, counts_dev[j]); counts_dev NULL: 1 for every key
+ *   insert       psk_ck_insert for this layout, without its dedup (the caller hands it fingerprints that are not in the table -- the new
+ *                ones of a batch -- or the re-insert stream of an expansion).  A bin placed directly takes counts_dev[i] (NULL: 1), a bin
+ *                that has to walk goes in hand with count 1 WHATEVER counts_dev[i] says (countingcuckoo.py:247), a swap exchanges pairs.
+ *                result_dev as there, and [9] the count of the leftover, [10] the count in hand of a suspended walk.  Enqueue only.
+ *   add_counts   u DISTINCT fingerprints as triples[3][u]: weights_dev[t] is added to the first bin that holds fingerprint t (the order of
+ *                check).  missed_dev[t] = 0: done, 1: no bin holds it, 2: the count would pass 2^32 - 1 and the bin is left as it is;
+ *                flags_dev[0] / [1] = how many 1s / 2s.  Distinct fingerprints own distinct bins: plain stores.  Enqueue only.
+ *   remove       u DISTINCT fingerprints as triples, requests_dev[t] removes of each: granted_dev[t] = min(requests, sum of the counts of
+ *                its copies), taken from the copies in the order of check; bins that reach 0 leave their row (rows are compacted to the
+ *                left, pairs together, vacated pairs zeroed, fill lowered) and are counted into emptied_dev[0].  bucket_size <= 32;
+ *                row_marks_dev: uint32[capacity], zero on entry and zero again afterwards.  Enqueue only. */
+int psk_cck_check(uint64_t capacity, uint32_t bucket_size, uint32_t fp_bits, const uint32_t *bins_dev, const uint32_t *fill_dev, int layout,
+                  const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, uint32_t *out, int device, void *stream);
+int psk_cck_present(uint64_t capacity, uint32_t bucket_size, const uint32_t *bins_dev, const uint32_t *fill_dev,
+                    const uint32_t *triples_dev, uint64_t n, uint8_t *out_dev, int device, void *stream);
+int psk_cck_place_apply(uint64_t capacity, uint32_t bucket_size, uint32_t *bins_dev, uint32_t *fill_dev, const uint32_t *triples_dev,
+                        const uint64_t *claims_dev, const uint32_t *pos_dev, uint64_t m, const uint8_t *d_dev, uint64_t prefix,
+                        const uint32_t *counts_dev, int device, void *stream);
+int psk_cck_insert(uint64_t capacity, uint32_t bucket_size, uint32_t max_swaps, uint32_t *bins_dev, uint32_t *fill_dev,
+                   const uint32_t *triples_dev, const uint32_t *counts_dev, uint64_t n, uint64_t start, uint64_t end, uint64_t budget,
+                   uint32_t *mt_state_dev, uint32_t *result_dev, int device, void *stream);
+int psk_cck_add_counts(uint64_t capacity, uint32_t bucket_size, uint32_t *bins_dev, uint32_t *fill_dev, const uint32_t *triples_dev,
+                       const uint32_t *weights_dev, uint64_t u, uint8_t *missed_dev, uint32_t *flags_dev, int device, void *stream);
+int psk_cck_remove(uint64_t capacity, uint32_t bucket_size, uint32_t *bins_dev, uint32_t *fill_dev, const uint32_t *triples_dev,
+                   const uint32_t *requests_dev, uint64_t u, uint32_t *row_marks_dev, uint32_t *granted_dev, uint32_t *emptied_dev,
+                   int device, void *stream);
+
 /* ------------------------------------------------------ table algebra (device pointers)
  * Streaming kernels over whole tables; also the local half of the multi-GPU merge.
  * or/and: bloom.py:371-428 union/intersection;  popcount: bloom.py:552-557;

@@ -2,7 +2,7 @@
 
 Drop-in names for the accelerated path (reference ``probables/__init__.py:3-53``):
 ``BloomFilter``, ``CountingBloomFilter``, ``CountMinSketch`` (+ ``CountMeanSketch`` /
-``CountMeanMinSketch``, ``HeavyHitters``, ``StreamThreshold``), ``ExpandingBloomFilter`` / ``RotatingBloomFilter``, ``QuotientFilter``, ``CuckooFilter``, their exceptions and the ``hash_function`` helpers.  Tables live in GPU HBM,
+``CountMeanMinSketch``, ``HeavyHitters``, ``StreamThreshold``), ``ExpandingBloomFilter`` / ``RotatingBloomFilter``, ``QuotientFilter``, ``CuckooFilter``, ``CountingCuckooFilter``, their exceptions and the ``hash_function`` helpers.  Tables live in GPU HBM,
 the work is done by hand-written gfx950 HIP kernels behind the C ABI in ``include/psk.h``.
 """
 
@@ -23,6 +23,7 @@ from .exceptions import (
 )
 from .quotientfilter import QuotientFilter
 from .cuckoo import CuckooFilter
+from .countingcuckoo import CountingCuckooBin, CountingCuckooFilter
 from .hashes import default_fnv_1a, default_md5, default_sha256, fnv_1a, fnv_1a_32, hash_with_depth_bytes, hash_with_depth_int
 
 __version__ = "0.1.0"
@@ -40,6 +41,8 @@ __all__ = [
     "QuotientFilter",
     "QuotientFilterError",
     "CuckooFilter",
+    "CountingCuckooFilter",
+    "CountingCuckooBin",
     "CuckooFilterFullError",
     "RotatingBloomFilterError",
     "InitializationError",

@@ -85,6 +85,12 @@ PROTOTYPES = {
     "psk_ck_place_apply": (_int, [_u64, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _int, _vp]),
     "psk_ck_insert": (_int, [_u64, _u32, _u32, _vp, _vp, _vp, _u64, _u64, _u64, _int, _u64, _vp, _vp, _int, _vp]),
     "psk_ck_remove": (_int, [_u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _int, _vp]),
+    "psk_cck_check": (_int, [_u64, _u32, _u32, _vp, _vp, *_KEYS, _int, _vp, _int, _vp]),
+    "psk_cck_present": (_int, [_u64, _u32, _vp, _vp, _vp, _u64, _vp, _int, _vp]),
+    "psk_cck_place_apply": (_int, [_u64, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _int, _vp]),
+    "psk_cck_insert": (_int, [_u64, _u32, _u32, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, _vp, _vp, _int, _vp]),
+    "psk_cck_add_counts": (_int, [_u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _int, _vp]),
+    "psk_cck_remove": (_int, [_u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _int, _vp]),
     "psk_table_or": (_int, [_vp, _vp, _u64, _int, _vp]),
     "psk_table_and": (_int, [_vp, _vp, _u64, _int, _vp]),
     "psk_table_popcount": (_int, [_vp, _u64, C.POINTER(_u64), _int, _vp]),

@@ -10,7 +10,7 @@
 // (d_t == which + 1).  The accepted prefix ends at min(e, first K): everything in front of it is placed exactly as the reference would,
 // slot = fill + (active claims in front), and nothing random has happened yet.
 //
-// Sequential insert (k_ck_insert).  One lane walks the triples in order and applies cuckoo.py:291-304 / :361-392 as written; the kicks
+// Sequential insert (k_ck_insert, psk_cuckoo.hpp: the counting filter runs the same walk over (fingerprint, count) pairs).  One lane walks the triples in order and applies cuckoo.py:291-304 / :361-392 as written; the kicks
 // draw from an MT19937 whose 625 words (random.getstate()) it reads from and writes back to a device buffer, so the table AND the
 // generator end as the reference's would.  The other 63 lanes of the wave only touch the rows of the next keys so that they are in cache.
 // Every loop has a bound valid data cannot reach (the rejection loop of _randbelow: 256 draws, each accepted with probability >= 1/2),
@@ -26,44 +26,7 @@
 
 namespace {
 
-constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr uint8_t kKick = 3;
-
-struct CkTable {
-    uint32_t *buckets, *fill;
-};
-
-__global__ __launch_bounds__(kBlock) void k_ck_present(CkGeom g, const uint32_t *buckets, const uint32_t *fill, const uint32_t *tr, uint64_t n, uint8_t *out)
-{
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
-    {
-        const CkTriple t{tr[i], tr[n + i], tr[2 * n + i]};
-        out[i] = t.i1 < g.capacity && t.i2 < g.capacity && ck_contains(g, buckets, fill, t) ? 1 : 0;
-    }
-}
-
-// ---- parallel placement
-// claims[p] = bucket << 32 | j << 1 | which, ascending; pos[which * m + j] = where key j's claim `which` stands in it.
-// -> the number of active claims of bucket b in front of position p that belong to keys t < j, counted up to `room`; kNone after kMaxWalk
-//    claims without an answer.  The caller then decides K, which only ends the accepted prefix early (the sequential kernel does that key
-//    exactly, kick or not): the map stays triangular, so the stable-prefix argument holds for it, and in front of the first such K it is the
-//    reference's.  A window holds at most capacity * B keys, 2 B claims per bucket on average; only crafted fingerprints get near kMaxWalk.
-constexpr uint32_t kMaxWalk = 1024;
-__device__ __forceinline__ uint32_t ck_active_before(const unsigned long long *claims, const uint8_t *d, uint32_t m, uint32_t p, uint32_t b, uint32_t j, uint32_t room)
-{
-    uint32_t c = 0;
-    if (p >= 2u * m) return room;  // (not a position of this claim list: a caller's garbage decides "no room")
-    for (uint32_t walked = 0; p > 0 && c < room; ++walked) {
-        if (walked == kMaxWalk) return kNone;
-        const unsigned long long cl = claims[--p];
-        if ((uint32_t)(cl >> 32) != b) break;
-        const uint32_t t = (uint32_t)cl >> 1, which = (uint32_t)cl & 1u;
-        if (t != j && t < m && d[t] == which + 1u) ++c;  // (t == j: the key's own other claim, when idx_1 == idx_2)
-    }
-    return c;
-}
-
+// ---- parallel placement (ck_active_before, k_ck_apply, k_ck_count: psk_cuckoo.hpp)
 // marks[0] = min j whose decision changed in this sweep, marks[1] = min j that decided K in this sweep
 __global__ __launch_bounds__(kBlock) void k_ck_sweep(CkGeom g, const uint32_t *fill, const uint32_t *tr, const unsigned long long *claims, const uint32_t *pos,
                                                      uint32_t m, const uint8_t *d_in, uint8_t *d_out, uint32_t *marks)
@@ -90,155 +53,7 @@ __global__ __launch_bounds__(kBlock) void k_ck_sweep(CkGeom g, const uint32_t *f
     }
 }
 
-// keys [0, p) with final decisions: write the fingerprints (fill is read, not written: k_ck_count follows)
-__global__ __launch_bounds__(kBlock) void k_ck_apply(CkGeom g, CkTable t, const uint32_t *tr, const unsigned long long *claims, const uint32_t *pos, uint32_t m,
-                                                     const uint8_t *d, uint32_t p)
-{
-    const uint32_t stride = gridDim.x * kBlock;
-    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < p; j += stride) {
-        const uint32_t which = d[j] - 1u;
-        if (which > 1u) continue;
-        const uint32_t b = tr[(uint64_t)(1 + which) * m + j];
-        if (b >= g.capacity) continue;
-        // (a key that decided 1 or 2 saw its whole segment within kMaxWalk, and this is the same walk)
-        const uint32_t c = ck_active_before(claims, d, m, pos[(uint64_t)which * m + j], b, j, g.B);
-        const uint32_t slot = c == kNone ? kNone : t.fill[b] + c;
-        if (slot < g.B) t.buckets[(uint64_t)b * g.B + slot] = tr[j];
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void k_ck_count(CkGeom g, uint32_t *fill, const uint32_t *tr, uint32_t m, const uint8_t *d, uint32_t p)
-{
-    const uint32_t stride = gridDim.x * kBlock;
-    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < p; j += stride) {
-        const uint32_t which = d[j] - 1u;
-        if (which > 1u) continue;
-        const uint32_t b = tr[(uint64_t)(1 + which) * m + j];
-        if (b < g.capacity) atomicAdd(fill + b, 1u);
-    }
-}
-
-// ---- sequential insert
-struct Mt {
-    uint32_t *w;  // 624 words in LDS
-    uint32_t idx;
-    bool bad;
-    __device__ uint32_t next()
-    {
-        if (idx >= 624u) {  // genrand_uint32 of _randommodule.c: regenerate the block
-            for (uint32_t k = 0; k < 624u; ++k) {
-                const uint32_t y = (w[k] & 0x80000000u) | (w[k == 623u ? 0u : k + 1u] & 0x7FFFFFFFu);
-                w[k] = w[k < 227u ? k + 397u : k - 227u] ^ (y >> 1) ^ ((y & 1u) ? 0x9908B0DFu : 0u);
-            }
-            idx = 0;
-        }
-        uint32_t y = w[idx++];
-        y ^= y >> 11;
-        y ^= (y << 7) & 0x9D2C5680u;
-        y ^= (y << 15) & 0xEFC60000u;
-        return y ^ (y >> 18);
-    }
-    // random._randbelow_with_getrandbits(n), 1 <= n < 2^31
-    __device__ uint32_t below(uint32_t n)
-    {
-        const uint32_t shift = (uint32_t)__clz(n);  // 32 - n.bit_length()
-        for (int tries = 0; tries < 256; ++tries) {
-            const uint32_t r = next() >> shift;
-            if (r < n) return r;
-        }
-        bad = true;
-        return 0;
-    }
-};
-
-// res: [0] status (0: stopped at `end` or out of budget in front of key res[1], 1: a walk failed at key res[1], 2: bad data, 3: out of budget
-//      inside the walk of key res[1]), [1] the first key not done, [2] the fingerprint left over by the failed walk, [3] fingerprints added
-//      to the count, [4] keys that began to walk, [5] steps used, [6] fingerprint in hand, [7] row and [8] swaps done of a suspended walk.
-//      A launch that finds res[0] == 3 takes that walk up at key `start`; every other launch starts with res[0] == 0.
-__global__ __launch_bounds__(64) void k_ck_insert(CkGeom g, CkTable t, uint32_t max_swaps, const uint32_t *tr, uint64_t n, uint64_t start, uint64_t end,
-                                                  int dedup, uint64_t budget, uint32_t *state, uint32_t *res)
-{
-    __shared__ uint32_t words[624];
-    const uint32_t lane = threadIdx.x;
-    for (uint32_t k = lane; k < 624u; k += 64u) words[k] = state[k];
-    __syncthreads();
-    Mt mt{words, state[624], false};
-    if (mt.idx > 624u) mt.idx = 624u;
-    uint32_t status = 0, leftover = 0, added = 0, walked = 0, hand = 0, hand_row = 0, hand_swaps = 0;
-    bool resume = res[0] == 3u;
-    uint64_t steps = 0, i = start;
-    bool stop = false;
-    for (uint64_t base = start; base < end && !stop; base += 64) {
-        {  // all lanes: pull the two rows of the next 64 keys towards the cache; nothing is decided here
-            const uint64_t k = base + lane;
-            if (k < end) {
-                const uint32_t r1 = tr[n + k], r2 = tr[2 * n + k];
-                if (r1 < g.capacity && r2 < g.capacity) {
-                    uint32_t a = t.buckets[(uint64_t)r1 * g.B], b = t.buckets[(uint64_t)r2 * g.B];
-                    asm volatile("" ::"v"(a), "v"(b));
-                }
-            }
-        }
-        if (lane != 0) continue;
-        const uint64_t top = base + 64 < end ? base + 64 : end;
-        for (i = base; i < top; ++i) {
-            if (steps >= budget) { stop = true; break; }
-            uint32_t fp, idx, s = 0;
-            if (resume) {  // (budget >= 1: this launch does at least one swap of it)
-                resume = false;
-                fp = res[6], idx = res[7], s = res[8];
-                if (idx >= g.capacity) { status = 2; stop = true; break; }
-            } else {
-                ++steps;
-                fp = tr[i];
-                const uint32_t i1 = tr[n + i], i2 = tr[2 * n + i];
-                if (i1 >= g.capacity || i2 >= g.capacity) { status = 2; stop = true; break; }
-                if (dedup && ck_contains(g, t.buckets, t.fill, CkTriple{fp, i1, i2})) continue;
-                uint32_t f = t.fill[i1], row = i1;
-                if (f >= g.B) f = t.fill[i2], row = i2;
-                if (f < g.B) {
-                    t.buckets[(uint64_t)row * g.B + f] = fp;
-                    t.fill[row] = f + 1u;
-                    ++added;
-                    continue;
-                }
-                ++walked;
-                idx = mt.below(2u) ? i2 : i1;  // random.choice([idx_1, idx_2])
-            }
-            bool placed = false, suspended = false;
-            for (; s < max_swaps && !mt.bad; ++s) {
-                if (steps >= budget) { suspended = true; break; }
-                ++steps;
-                uint32_t *slot = t.buckets + (uint64_t)idx * g.B + mt.below(g.B);  // random.randint(0, bucket_size - 1)
-                const uint32_t out = *slot;
-                *slot = fp;
-                fp = out;
-                const CkTriple e = ck_triple_of(g, fp);
-                idx = idx == e.i1 ? e.i2 : e.i1;
-                const uint32_t fe = t.fill[idx];
-                if (fe < g.B) {
-                    t.buckets[(uint64_t)idx * g.B + fe] = fp;
-                    t.fill[idx] = fe + 1u;
-                    ++added;
-                    placed = true;
-                    break;
-                }
-            }
-            if (mt.bad) { status = 2; stop = true; break; }
-            if (suspended) { status = 3, hand = fp, hand_row = idx, hand_swaps = s; stop = true; break; }
-            if (!placed) { status = 1, leftover = fp; stop = true; break; }
-        }
-    }
-    __syncthreads();
-    if (lane == 0) {
-        res[0] = status, res[1] = (uint32_t)i, res[2] = leftover, res[3] = added, res[4] = walked, res[5] = (uint32_t)(steps > 0xFFFFFFFFull ? 0xFFFFFFFFull : steps);
-        res[6] = hand, res[7] = hand_row, res[8] = hand_swaps;
-        state[624] = mt.idx;
-    }
-    for (uint32_t k = lane; k < 624u; k += 64u) state[k] = words[k];
-}
-
-// ---- ordered removal
+// ---- ordered removal (k_ck_rm_compact: psk_cuckoo.hpp)
 // -> copies of fp in the row; *slot = where copy number `want` stands (kNone: there are fewer)
 __device__ __forceinline__ uint32_t ck_copies(const CkGeom &g, const CkTable &t, uint32_t row, uint32_t fp, uint32_t want, uint32_t *slot)
 {
@@ -274,28 +89,6 @@ __global__ __launch_bounds__(kBlock) void k_ck_rm_mark(CkGeom g, CkTable t, cons
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_ck_rm_compact(CkGeom g, CkTable t, const uint32_t *tr, uint64_t n, uint32_t *marks)
-{
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        for (int which = 0; which < 2; ++which) {
-            const uint32_t row = tr[(uint64_t)(1 + which) * n + i];
-            if (row >= g.capacity || !marks[row]) continue;
-            const uint32_t gone = atomicExch(marks + row, 0u);  // one lane gets the mask, and with it the row
-            if (!gone) continue;
-            uint32_t *p = t.buckets + (uint64_t)row * g.B;
-            const uint32_t f = min(t.fill[row], g.B);
-            uint32_t w = 0;
-            for (uint32_t s = 0; s < f; ++s) {
-                const uint32_t v = p[s];
-                if (!((gone >> s) & 1u)) p[w++] = v;
-            }
-            for (uint32_t s = w; s < f; ++s) p[s] = 0;
-            t.fill[row] = w;
-        }
-    }
-}
-
 int ck_geom(uint64_t capacity, uint32_t bucket_size, uint32_t fp_bits, CkGeom *g)
 {
     if (!ck_make_geom(capacity, bucket_size, fp_bits, g))
@@ -317,7 +110,7 @@ extern "C" int psk_ck_present(uint64_t capacity, uint32_t bucket_size, const uin
     if (n && (!triples_dev || !out_dev)) return fail(PSK_EINVAL, "NULL argument");
     PSK_USE_DEVICE(device);
     if (!n) return PSK_OK;
-    hipLaunchKernelGGL(k_ck_present, dim3(grid_for_keys(n)), dim3(kBlock), 0, (hipStream_t)stream, g, buckets_dev, fill_dev, triples_dev, n, out_dev);
+    hipLaunchKernelGGL(k_ck_present<1>, dim3(grid_for_keys(n)), dim3(kBlock), 0, (hipStream_t)stream, g, buckets_dev, fill_dev, triples_dev, n, out_dev);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
 }
@@ -350,8 +143,8 @@ extern "C" int psk_ck_place_apply(uint64_t capacity, uint32_t bucket_size, uint3
     if (!prefix) return PSK_OK;
     hipStream_t st = (hipStream_t)stream;
     const CkTable t{buckets_dev, fill_dev};
-    hipLaunchKernelGGL(k_ck_apply, dim3(grid_for_keys(prefix)), dim3(kBlock), 0, st, g, t, triples_dev, (const unsigned long long *)claims_dev, pos_dev, (uint32_t)m, d_dev,
-                       (uint32_t)prefix);
+    hipLaunchKernelGGL(k_ck_apply<1>, dim3(grid_for_keys(prefix)), dim3(kBlock), 0, st, g, t, triples_dev, (const unsigned long long *)claims_dev, pos_dev, (uint32_t)m, d_dev,
+                       (uint32_t)prefix, (const uint32_t *)nullptr);
     hipLaunchKernelGGL(k_ck_count, dim3(grid_for_keys(prefix)), dim3(kBlock), 0, st, g, fill_dev, triples_dev, (uint32_t)m, d_dev, (uint32_t)prefix);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
@@ -367,7 +160,7 @@ extern "C" int psk_ck_insert(uint64_t capacity, uint32_t bucket_size, uint32_t m
     if (!buckets_dev || !fill_dev || !mt_state_dev || !result_dev || (n && !triples_dev)) return fail(PSK_EINVAL, "NULL argument");
     PSK_USE_DEVICE(device);
     const CkTable t{buckets_dev, fill_dev};
-    hipLaunchKernelGGL(k_ck_insert, dim3(1), dim3(64), 0, (hipStream_t)stream, g, t, max_swaps, triples_dev, n, start, end, dedup, budget, mt_state_dev, result_dev);
+    hipLaunchKernelGGL(k_ck_insert<1>, dim3(1), dim3(64), 0, (hipStream_t)stream, g, t, max_swaps, triples_dev, (const uint32_t *)nullptr, n, start, end, dedup, budget, mt_state_dev, result_dev);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
 }
@@ -385,7 +178,7 @@ extern "C" int psk_ck_remove(uint64_t capacity, uint32_t bucket_size, uint32_t *
     hipStream_t st = (hipStream_t)stream;
     const CkTable t{buckets_dev, fill_dev};
     hipLaunchKernelGGL(k_ck_rm_mark, dim3(grid_for_keys(n)), dim3(kBlock), 0, st, g, t, triples_dev, rank_dev, n, row_marks_dev, out_dev);
-    hipLaunchKernelGGL(k_ck_rm_compact, dim3(grid_for_keys(n)), dim3(kBlock), 0, st, g, t, triples_dev, n, row_marks_dev);
+    hipLaunchKernelGGL(k_ck_rm_compact<1>, dim3(grid_for_keys(n)), dim3(kBlock), 0, st, g, t, triples_dev, n, row_marks_dev);
     HIP_TRY(hipGetLastError());
     return PSK_OK;
 }

@@ -390,12 +390,42 @@ class CuckooFilter:
         return out
 
     # ------------------------------------------------------------------ insert
+    # What CountingCuckooFilter (countingcuckoo.py) replaces: the entries that know the slot layout, what a placed fingerprint adds to the
+    # totals, what a failed walk leaves over, and what has to happen to the batch before that leftover is dealt with.
+    _EXPAND_FAILED = "The CuckooFilter failed to expand"
+    _HOST_DEDUP = False  # True: the insert kernel has no dedup of its own, every policy takes the survivors on the host
+
     def _present(self, tr):
         n = int(tr.shape[1])
         out = torch.empty(n, dtype=torch.uint8, device=self._dev())
         if n:
-            N.check(N.lib().psk_ck_present(*self._geom(), *self._table(), tr.data_ptr(), n, out.data_ptr(), self._device, self._stream))
+            N.check(self._present_entry()(*self._geom(), *self._table(), tr.data_ptr(), n, out.data_ptr(), self._device, self._stream))
         return out.view(torch.bool)
+
+    def _present_entry(self):
+        return N.lib().psk_ck_present
+
+    def _slots_used(self) -> int:
+        return self._elements_added
+
+    def _added(self, k: int) -> None:
+        self._elements_added += k
+
+    def _place_apply(self, window, claims, pos, w: int, d, prefix: int, counts) -> None:
+        N.check(N.lib().psk_ck_place_apply(*self._geom(), *self._table(), window.data_ptr(), claims.data_ptr(), pos.data_ptr(), w, d.data_ptr(), prefix,
+                                           self._device, self._stream))
+
+    def _insert_launch(self, tr, start: int, end: int, dedup: bool, mt, res, counts) -> None:
+        N.check(N.lib().psk_ck_insert(*self._geom(), min(self._max_swaps, _NONE), *self._table(), tr.data_ptr(), int(tr.shape[1]), start, end, int(dedup),
+                                      SEQ_BUDGET, mt.data_ptr(), res.data_ptr(), self._device, self._stream))
+
+    def _leftover(self, res):
+        """what a failed walk leaves over, from the words of its launch"""
+        return int(res[2]) & _NONE
+
+    def _walk_failed(self, at: int, leftover):
+        """the walk of the key at batch position `at` failed -> the leftover to expand with (or to drop)"""
+        return leftover
 
     def _survivors(self, tr):
         """the keys an ``add`` loop would insert: first occurrence of their fingerprint in the batch, fingerprint not in the table
@@ -410,11 +440,11 @@ class CuckooFilter:
         at = torch.nonzero(keep).reshape(-1)
         return tr[:, at].contiguous(), at
 
-    def _place(self, window) -> int:
+    def _place(self, window, counts=None) -> int:
         """parallel placement of the longest provably final prefix of `window` ((3, w) triples) -> keys placed.  The triples are distinct and
         not in the table, so each placed one takes a free slot: no more than the free slots can be placed and the window ends there (which
         also keeps a bucket's claim segment, walked by every sweep, at 2 * bucket_size claims on average)"""
-        free = self._capacity * self._bucket_size - self._elements_added
+        free = self._capacity * self._bucket_size - self._slots_used()
         window = window[:, :max(free, 1)].contiguous()
         w = int(window.shape[1])
         if w == 0:
@@ -441,40 +471,40 @@ class CuckooFilter:
         stats["sweeps"] = stats.get("sweeps", 0) + sweeps
         stats.setdefault("first_place", (sweeps, prefix))  # of the first placement of the call: (sweeps it took, keys it placed)
         if prefix:
-            N.check(L.psk_ck_place_apply(*self._geom(), *self._table(), window.data_ptr(), claims.data_ptr(), pos.data_ptr(), w, d_old.data_ptr(), prefix,
-                                         self._device, self._stream))
-            self._elements_added += prefix
+            self._place_apply(window, claims, pos, w, d_old, prefix, counts)
+            self._added(prefix)
         return prefix
 
-    def _sequential(self, tr, start: int, end: int, dedup: bool, mt):
-        """-> (status, first key not done, leftover fingerprint, keys that walked)"""
+    def _sequential(self, tr, start: int, end: int, dedup: bool, mt, counts=None):
+        """-> (status, first key not done, what the failed walk left over, keys that walked)"""
         res = torch.zeros(12, dtype=torch.int32, device=self._dev())
         walked, stats, t0 = 0, self.last_insert_stats, time.perf_counter()
         while True:  # one launch, or as many as a walk that outlives the launch's budget needs: `res` carries it from one to the next
-            N.check(N.lib().psk_ck_insert(*self._geom(), min(self._max_swaps, _NONE), *self._table(), tr.data_ptr(), int(tr.shape[1]), start, end, int(dedup),
-                                          SEQ_BUDGET, mt.data_ptr(), res.data_ptr(), self._device, self._stream))
-            status, start, left, added, began = (int(x) & _NONE for x in res[:5].tolist())
+            self._insert_launch(tr, start, end, dedup, mt, res, counts)
+            words = res.tolist()
+            status, start, _, added, began = (int(x) & _NONE for x in words[:5])
             if status == 2:
                 raise NativeLibraryError("psk_ck_insert: the table or the key stream is not a cuckoo filter's (index outside the table, or no draw accepted)")
-            self._elements_added += added
+            self._added(added)
             walked += began
             # (the read of `res` waited for the kernel: steps and seconds of the launches, what SEQ_BUDGET is sized from)
-            stats["sequential_steps"] = stats.get("sequential_steps", 0) + (int(res[5]) & _NONE)
+            stats["sequential_steps"] = stats.get("sequential_steps", 0) + (int(words[5]) & _NONE)
             if status != 3:
                 stats["sequential_seconds"] = stats.get("sequential_seconds", 0.0) + time.perf_counter() - t0
-                return status, start, left, walked
+                return status, start, self._leftover(words) if status == 1 else None, walked
 
-    def _run(self, tr, dedup: bool, mt, expanding: bool = False) -> None:
-        """the stream `tr` through ``add`` (dedup) or through the re-insert loop of ``_expand_logic`` (not dedup)"""
+    def _run(self, tr, dedup: bool, mt, expanding: bool = False, counts=None) -> None:
+        """the stream `tr` through ``add`` (dedup) or through the re-insert loop of ``_expand_logic`` (not dedup; `counts`: what the counting
+        filter's bins carry)"""
         policy, stats = self._insert_policy, self.last_insert_stats
         at = None
-        if dedup and policy != "sequential":
+        if dedup and (policy != "sequential" or self._HOST_DEDUP):
             tr, at = self._survivors(tr)
         m = int(tr.shape[1])
         done, parallel = 0, policy != "sequential"
         while done < m:
             if parallel:
-                placed = self._place(tr[:, done:done + PAR_WINDOW])
+                placed = self._place(tr[:, done:done + PAR_WINDOW], None if counts is None else counts[done:done + PAR_WINDOW])
                 stats["parallel_keys"] = stats.get("parallel_keys", 0) + placed
                 done += placed
                 if done >= m:
@@ -482,22 +512,24 @@ class CuckooFilter:
                 if policy == "auto" and placed < PAR_MIN:
                     parallel = False
             end = done + 1 if policy == "parallel" else min(m, done + SEQ_CHUNK)
-            status, nxt, leftover, walked = self._sequential(tr, done, end, dedup, mt)
+            status, nxt, leftover, walked = self._sequential(tr, done, end, dedup, mt, counts)
             stats["sequential_keys"] = stats.get("sequential_keys", 0) + nxt - done + (status == 1)
             stats["kicked_keys"] = stats.get("kicked_keys", 0) + walked
             done = nxt
             if status != 1:
                 continue
             if expanding:
-                raise CuckooFilterFullError("The CuckooFilter failed to expand")
+                raise CuckooFilterFullError(self._EXPAND_FAILED)
+            failed = int(at[done]) if at is not None else done  # the key of the batch that could not be inserted
+            leftover = self._walk_failed(failed, leftover)
             if not self._auto_expand:
                 err = CuckooFilterFullError(f"The {self.__class__.__name__} is currently full")
-                err.index = int(at[done]) if at is not None else done  # the key of the batch that could not be inserted
+                err.index = failed
                 raise err
             try:
                 self._expand_with(leftover, mt)
             except CuckooFilterFullError as err:
-                err.index = int(at[done]) if at is not None else done
+                err.index = failed
                 raise
             done += 1
             tr = self._triples_of_fingerprints(tr[0])  # the rest of the caller's stream, at the new capacity
