@@ -430,7 +430,11 @@ int psk_cck_remove(uint64_t capacity, uint32_t bucket_size, uint32_t *bins_dev, 
  * Streaming kernels over whole tables; also the local half of the multi-GPU merge.
  * or/and: bloom.py:371-428 union/intersection;  popcount: bloom.py:552-557;
  * add_sat_i32: countminsketch.py:380-391 join;  add_u32: countingbloom.py:296-298 union;
- * or_reduce: dst[w] = OR_j src[j*slice_words + w] (the reduce step of allreduce(OR): RCCL has no OR op) */
+ * or_reduce: dst[w] = OR_j src[j*slice_words + w] (the reduce step of allreduce(OR): RCCL has no OR op)
+ * psk_table_add_sat_i32, psk_table_add_u32 and psk_cbf_intersect know nothing of handles: a caller who applies them to the table of a
+ * CountMinSketch / CountingBloomFilter handle owes that handle a psk_rescan_bound afterwards.  The handle's unordered adds and removes
+ * choose between wrapping atomics and the saturating path by PSK_CTR_ABS_BOUND; with a stale bound, counters that the sum has brought
+ * close to a rail wrap under the next psk_cbf_add / psk_cms_add instead of stopping there. */
 int psk_table_or(void *dst, const void *src, uint64_t nwords32, int device, void *stream);
 int psk_table_and(void *dst, const void *src, uint64_t nwords32, int device, void *stream);
 int psk_table_popcount(const void *tab, uint64_t nwords32, uint64_t *out_host, int device, void *stream);

@@ -318,6 +318,7 @@ class CountingBloomFilter(BloomFilter):
         N.check(L.psk_table_add_u32(t.ptr, second._tab.ptr, self.number_bits, C.byref(ov), t.device, t.stream))
         if ov.value:  # the reference's array('I') store raises here
             raise OverflowError("unsigned int is greater than maximum")
+        t.written()  # the sums went in through the bare pointer: the result's wrap-free bound is rescanned, as join does
         res.elements_added = res.estimate_elements()
         return res
 
@@ -332,6 +333,7 @@ class CountingBloomFilter(BloomFilter):
         N.check(N.lib().psk_cbf_intersect(t.ptr, self._tab.ptr, second._tab.ptr, self.number_bits, C.byref(ov), t.device, t.stream))
         if ov.value:  # the reference's array('I') store raises here
             raise OverflowError("unsigned int is greater than maximum")
+        t.written()  # (as in union: an add_many onto the result must see how close its counters stand to 2^32 - 1)
         res.elements_added = res.estimate_elements()
         return res
 

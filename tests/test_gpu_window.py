@@ -375,3 +375,27 @@ def test_window_tile_sizes_agree(pa, oracle, N, tile):
         _same(cbf, oc)
     finally:
         N.set_option("update_window_tile", old)
+
+
+@pytest.mark.parametrize("op", ["union", "intersection"])
+def test_set_algebra_sees_the_batches_waiting_on_both_operands(pa, oracle, N, op):
+    """small add batches wait in the windows of BOTH operands when union / intersection take their tables: the result is the sum of the
+    flushed tables (countingbloom.py:235-238, :296-298), and the operands end as the oracle's"""
+    a = pa.CountingBloomFilter(est_elements=3_600_000, false_positive_rate=0.01)
+    b = pa.CountingBloomFilter(est_elements=3_600_000, false_positive_rate=0.01)
+    m, k = a.number_bits, a.number_hashes
+    oa, ob = oracle.OracleCBF(m, k), oracle.OracleCBF(m, k)
+    ka, kb = oracle.gen_keys16(61, 300_000), oracle.gen_keys16(61 + 200_000, 300_000)  # a third of the keys on both sides
+    for flt, oc, kk in ((a, oa, ka), (b, ob, kb)):
+        for part in (kk[:200_000], kk[200_000:]):
+            flt.add_many(_dev(part))
+            oc.update_keys(part)
+        assert flt._tab.get_option("window_pending_batches") == 2
+    res = getattr(a, op)(b)
+    assert a._tab.get_option("window_pending_batches") == b._tab.get_option("window_pending_batches") == 0
+    x, y = oa.bloom.astype(np.int64), ob.bloom.astype(np.int64)
+    want = x + y if op == "union" else np.where((x > 0) & (y > 0), x + y, 0)
+    assert np.array_equal(_table(res).astype(np.int64), want)
+    assert res.elements_added == (oa.union(ob) if op == "union" else oa.intersection(ob)).els_estimate
+    _same(a, oa)
+    _same(b, ob)
