@@ -125,7 +125,8 @@ int psk_device_count(int *count);
  * "update_window_tile", "update_window_wide", "update_window_force_fail", "ragged_sort", "host_poll_us" (how long a tiny PSK_HOST call
  * polls its completion mailbox before it waits for the stream; 0 = never poll); read-only counters "cbf_ordered_replays",
  * "update_window_folds", "update_window_replays", "cms_small_weights_used", "cbf_lookup_shadow_hits", "cms_running_fast",
- * "cms_running_sequential" (psk_cms_add_running calls that took the parallel passes / the one-lane kernel).
+ * "cms_running_sequential" (psk_cms_add_running calls that took the parallel passes / the one-lane kernel), "cms_update_running_fast",
+ * "cms_update_running_sequential" (the same for psk_cms_update_running).
  * The bench build (-DPSK_BENCH_KNOBS=1, libpsk_hip_knobs.so) has one more option, "part_debug": the ablation / phase-profile bits of the
  * measuring tools; this library answers "unknown option" to it.  The A/B switches of experiments that were measured and dropped are gone
  * with their code (NOTES.md). */
@@ -294,6 +295,18 @@ int psk_cms_add_running(psk_sketch *s, int layout, const void *data, const uint6
                         uint32_t key_len, const int32_t *weights /* NULL = 1 */, int where, int query,
                         int64_t els_in, void *out /* int32[n]; int64[n] for PSK_Q_MEANMIN */,
                         int64_t *els_out, void *stream);
+/* countminsketch.py:267-321 for a whole ORDERED batch of adds AND removes: weights int32[n] or NULL (= +1), w >= 0 adds w, w < 0 removes
+ * -w; every int32 is valid (INT32_MIN removes 2^31).  out[i], the table, *els_out and the PSK_CTR_SATURATED / PSK_CTR_ABS_BOUND tallies end
+ * exactly as psk_cms_update_ordered(..., PSK_OP_SIGNED, ...) leaves them for the same stream.  An op on a bin is the map
+ * x -> clamp(x + w, INT32_MIN, INT32_MAX); such maps compose to maps of the same form, (a, lo, hi): x -> min(hi, max(lo, x + a)), so the
+ * bin's value after op i is a segmented scan of maps applied to the table -- the passes, chunks, eligibility (depth <= 64, width <= 2^32,
+ * else the one-lane kernel) and the PSK_HOST / PSK_DEVICE conventions of psk_cms_add_running; n == 0 runs nothing and returns els_in.
+ * Read-only options "cms_update_running_fast" / "cms_update_running_sequential" count the calls either way ("cms_running_*" are
+ * psk_cms_add_running's alone). */
+int psk_cms_update_running(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n,
+                           uint32_t key_len, const int32_t *weights /* NULL = +1 */, int where, int query,
+                           int64_t els_in, void *out /* int32[n]; int64[n] for PSK_Q_MEANMIN */,
+                           int64_t *els_out, void *stream);
 
 /* ------------------------------------------------------------------ hashing
  * out[i*depth + j] = fnv_1a(key_i, seed=j)  (hashes.py:71-103); layout != PSK_KEYS_HASHES */

@@ -5,7 +5,8 @@ Drop-in for the hot path of ``probables.CountMinSketch`` (``probables/countminsk
 Single-key ``add`` / ``remove`` run the reference semantics literally (ordered kernel: exact return value,
 exact int32 / int64 clamps); ``add_many`` / ``remove_many`` are unordered atomic batches whose final table is
 bit-exact whenever it does not depend on the order (same-sign weights, or no bin touching a rail);
-``add_many_ordered`` is the batch form of ``add``: what the reference's loop returns for every key of an ordered batch.
+``add_many_ordered`` is the batch form of ``add``: what the reference's loop returns for every key of an ordered batch;
+``update_many_ordered`` / ``remove_many_ordered`` are the same for batches with removes in them.
 
 ``StreamThreshold`` and ``HeavyHitters`` (countminsketch.py:532-843) track a dict that every ``add`` feeds with its return value;
 their ``add_many`` is ``add_many_ordered`` plus the dict rule, written as the two pure functions ``threshold_rule`` / ``hitters_rule``.
@@ -327,19 +328,10 @@ class CountMinSketch:
     def remove_many(self, keys, num_els=None) -> None:
         self._update_batch(N.lib().psk_cms_remove, self._batch(keys), num_els)
 
-    def _add_running(self, b: KeyBatch, num_els):
-        """``psk_cms_add_running``: every op's return value of the ordered batch, on the batch's side"""
-        w = num_els
-        if w is not None:
-            if hasattr(w, "is_cuda"):  # a torch tensor (a device one costs one small reduction and a synchronisation here)
-                neg = bool(w.numel()) and int(w.min().item()) < 0
-            else:
-                a = np.asarray(w)
-                neg = bool(a.size) and int(a.min()) < 0
-            if neg:
-                raise ValueError("add_many_ordered: num_els must be >= 0 (removes are not part of an ordered add batch)")
+    def _running(self, fn, b: KeyBatch, w, lo: int):
+        """``psk_cms_add_running`` / ``psk_cms_update_running``: every op's return value of the ordered batch, on the batch's side"""
         keep: list = []
-        w_addr, _ = weights_arg(w, b.n, np.int32, b.where, keep, 0, _I32_MAX, self._tab.device)
+        w_addr, _ = weights_arg(w, b.n, np.int32, b.where, keep, lo, _I32_MAX, self._tab.device)
         wide = self._query == "mean-min"
         addr, fin = self._tab.out_buffer(b, b.n, np.int64 if wide else np.int32, _torch_dtype("int64" if wide else "int32"))
         els_in = self.elements_added
@@ -351,10 +343,71 @@ class CountMinSketch:
         else:
             els = C.c_int64(0)
             els_addr = C.addressof(els)
-        N.check(N.lib().psk_cms_add_running(self._tab.handle, *b.args(), w_addr, b.where, _QUERIES[self._query], els_in, addr or None, els_addr,
-                                            self._tab.stream))
+        N.check(fn(self._tab.handle, *b.args(), w_addr, b.where, _QUERIES[self._query], els_in, addr or None, els_addr, self._tab.stream))
         self._els_added = int(els.item()) if b.where == N.DEVICE else els.value
         return fin()
+
+    @staticmethod
+    def _weight_range(w):
+        """(min, max) of a weight argument as Python integers, None for an empty one (a device tensor costs one small reduction and a
+        synchronisation here)"""
+        if hasattr(w, "is_cuda"):
+            return (int(w.min().item()), int(w.max().item())) if w.numel() else None
+        a = np.asarray(w)
+        return (int(a.min()), int(a.max())) if a.size else None
+
+    def _add_running(self, b: KeyBatch, num_els):
+        w = num_els
+        if w is not None:
+            if hasattr(w, "is_cuda"):  # a torch tensor (a device one costs one small reduction and a synchronisation here)
+                neg = bool(w.numel()) and int(w.min().item()) < 0
+            else:
+                a = np.asarray(w)
+                neg = bool(a.size) and int(a.min()) < 0
+            if neg:
+                raise ValueError("add_many_ordered: num_els must be >= 0 (removes are not part of an ordered add batch)")
+        return self._running(N.lib().psk_cms_add_running, b, num_els, 0)
+
+    def _update_running(self, b: KeyBatch, signed_num_els):
+        w = signed_num_els
+        if w is not None and not (hasattr(w, "is_cuda") and w.dtype.is_signed and w.element_size() <= 4):  # (an int32 tensor cannot be outside)
+            r = self._weight_range(w)
+            if r and (r[0] < _I32_MIN or r[1] > _I32_MAX):
+                raise ValueError("update_many_ordered: weights must lie in [-2**31, 2**31 - 1]; update_ordered takes int64 weights "
+                                 "(and walks the batch on its sequential kernel)")
+        return self._running(N.lib().psk_cms_update_running, b, signed_num_els, _I32_MIN)
+
+    def update_many_ordered(self, keys, signed_num_els):
+        """the batch form of a mixed stream of ``add`` and ``remove`` (countminsketch.py:257-321): ``w >= 0`` adds ``w``, ``w < 0``
+        removes ``-w``; the table and ``elements_added`` end as the loop of single calls leaves them and entry i of the result is what
+        that loop's i-th call returns under the current ``query_type`` -- int32 (int64 for 'mean-min'), numpy for host batches, a torch
+        tensor for device batches.  Weights are int32 (``-2**31`` removes 2^31); anything outside raises ValueError before anything
+        changes -- ``update_ordered`` keeps its int64 weights and its sequential kernel."""
+        return self._update_running(self._batch(keys), signed_num_els)
+
+    def update_alt_many_ordered(self, hashes, signed_num_els):
+        """``update_many_ordered`` for pre-computed hashes (a (n, depth) uint64 array / tensor)"""
+        return self._update_running(self._alt(hashes), signed_num_els)
+
+    @classmethod
+    def _negated(cls, num_els):
+        """the weights of ``remove_many_ordered`` as ``update_many_ordered`` takes them"""
+        if num_els is None:
+            return -1
+        r = cls._weight_range(num_els)
+        if r and (r[0] < 0 or r[1] > _I32_MAX):
+            raise ValueError("remove_many_ordered: num_els must lie in [0, 2**31 - 1] (update_many_ordered removes 2**31 with the weight -2**31)")
+        if hasattr(num_els, "is_cuda"):
+            return -num_els
+        return -np.asarray(num_els, dtype=np.int64) if np.ndim(num_els) else -int(num_els)
+
+    def remove_many_ordered(self, keys, num_els=None):
+        """the batch form of ``remove`` (countminsketch.py:290-321): ``update_many_ordered`` with the weights negated; ``num_els``
+        must be >= 0"""
+        return self._update_running(self._batch(keys), self._negated(num_els))
+
+    def remove_alt_many_ordered(self, hashes, num_els=None):
+        return self._update_running(self._alt(hashes), self._negated(num_els))
 
     def add_many_ordered(self, keys, num_els=None):
         """the batch form of ``add`` (countminsketch.py:257-288): the table and ``elements_added`` end as the loop
@@ -518,38 +571,75 @@ class StreamThreshold(CountMinSketch):
         """countminsketch.py:817-835"""
         return self._removed(key, super().remove_alt(hashes, num_els))
 
+    def _replay(self, keys, res, neg) -> None:
+        """the dict after the ordered batch.  An add stores ``res >= threshold`` (:800-803), a remove stores it as well and pops the key
+        otherwise (:831-834): every op at or above the threshold matters, and a remove below it matters only while the dict holds
+        something -- it is empty and stays so when nothing of the batch reaches the threshold.  ``neg``: which ops remove, on the side of
+        ``res`` (None: none, True: all).  The selected ops alone come to the host and are replayed in op order."""
+        sel = res >= self._threshold
+        if neg is not None and (self._meets or bool(sel.any())):
+            sel = sel | neg
+        if hasattr(res, "is_cuda"):
+            import torch  # noqa: PLC0415
+
+            at = torch.nonzero(sel).flatten()
+            idx, vals = at.cpu().numpy(), res[at].cpu().numpy()
+        else:
+            idx = np.nonzero(sel)[0]
+            vals = res[idx]
+        if not idx.size:
+            return
+        if isinstance(keys, list):
+            picked = [keys[i] for i in idx.tolist()]
+        elif hasattr(keys, "is_cuda") and keys.is_cuda:  # only the selected rows leave the device
+            import torch  # noqa: PLC0415
+
+            picked = _batch_keys(keys[torch.from_numpy(idx).to(keys.device)])
+        else:
+            allk = _batch_keys(keys)
+            picked = [allk[i] for i in idx.tolist()]
+        if neg is None:
+            threshold_rule(self._meets, picked, vals.tolist(), self._threshold)
+            return
+        for key, r in zip(picked, vals.tolist()):  # (selected and below the threshold: a remove)
+            if r >= self._threshold:
+                self._meets[key] = r
+            else:
+                self._meets.pop(key, None)
+
     def add_many(self, keys, num_els=None):
         """``add`` for every key of the ordered batch: the sketch through ``add_many_ordered``; of the results only those that reached
         the threshold matter to the dict -- they are selected where the results lie and stored in op order.  Returns the results."""
         res = self.add_many_ordered(keys, num_els)
-        if hasattr(res, "is_cuda"):
-            import torch  # noqa: PLC0415
-
-            at = torch.nonzero(res >= self._threshold).flatten()
-            idx, vals = at.cpu().numpy(), res[at].cpu().numpy()
-        else:
-            idx = np.nonzero(res >= self._threshold)[0]
-            vals = res[idx]
-        if idx.size:
-            if isinstance(keys, list):
-                picked = [keys[i] for i in idx.tolist()]
-            elif hasattr(keys, "is_cuda") and keys.is_cuda:  # only the selected rows leave the device
-                import torch  # noqa: PLC0415
-
-                picked = _batch_keys(keys[torch.from_numpy(idx).to(keys.device)])
-            else:
-                allk = _batch_keys(keys)
-                picked = [allk[i] for i in idx.tolist()]
-            threshold_rule(self._meets, picked, vals.tolist(), self._threshold)
+        self._replay(keys, res, None)
         return res
 
     def remove_many(self, keys, num_els=None):
-        """``remove`` for every key of an ordered HOST batch.  Exact and slow: the removes walk the batch on one lane
-        (``update_ordered``'s sequential kernel); there is no parallel ordered remove."""
-        allk = _batch_keys(keys)
-        res = self._ordered(self._batch(keys), 1 if num_els is None else num_els, N.OP_REMOVE)
-        for key, r in zip(allk, res.tolist()):
-            self._removed(key, r)
+        """``remove`` for every key of an ordered batch, host or device: the sketch through ``remove_many_ordered`` (the parallel signed
+        passes of ``psk_cms_update_running``), the dict replayed on the host in op order.  Returns the results."""
+        res = self.remove_many_ordered(keys, num_els)
+        self._replay(keys, res, True)
+        return res
+
+    def update_many(self, keys, signed_num_els):
+        """a mixed ordered batch: ``w >= 0`` is ``add(key, w)``, ``w < 0`` is ``remove(key, -w)``.  The sketch goes through
+        ``update_many_ordered``; the dict is replayed on the host in op order, add ops by ``threshold_rule``, remove ops by the rule of
+        ``remove`` (countminsketch.py:831-834).  Returns the results."""
+        res = self.update_many_ordered(keys, signed_num_els)
+        w = signed_num_els
+        if w is None:
+            neg = None
+        elif hasattr(w, "is_cuda"):
+            neg = (w < 0).to(res.device) if hasattr(res, "is_cuda") else (w < 0).numpy()
+        elif np.ndim(w) == 0:
+            neg = True if int(w) < 0 else None
+        else:
+            neg = np.asarray(w) < 0
+            if hasattr(res, "is_cuda"):
+                import torch  # noqa: PLC0415
+
+                neg = torch.from_numpy(neg).to(res.device)
+        self._replay(keys, res, neg)
         return res
 
     def join(self, second) -> None:
@@ -623,6 +713,7 @@ class HeavyHitters(CountMinSketch):
         raise NotSupportedError(self._NO_REMOVE)
 
     remove_alt_many = remove_many
+    update_many_ordered = update_alt_many_ordered = remove_many_ordered = remove_alt_many_ordered = remove_many
 
     def clear(self) -> None:
         super().clear()

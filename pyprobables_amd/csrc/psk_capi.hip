@@ -178,6 +178,8 @@ int64_t g_small_weights_used = 0;          // weighted CMS adds that travelled i
 int64_t g_cbf_shadow_hits = 0;             // nibble-slice lookups that loaded kept images (psk_sketch::shadow)
 int64_t g_running_fast = 0;                // psk_cms_add_running calls that took the parallel passes
 int64_t g_running_sequential = 0;          // ... and the one-lane kernel
+int64_t g_update_running_fast = 0;         // psk_cms_update_running calls that took the parallel passes
+int64_t g_update_running_sequential = 0;   // ... and the one-lane kernel
 // Process DEFAULTS of the per-sketch options, in HandleOpt order.  Nothing but the option calls and resolve_options touches them: the engine
 // reads psk_sketch::eff.
 static int64_t g_sketch_default[HO_COUNT] = {
@@ -253,6 +255,8 @@ const OptDesc kOptions[] = {
     {"cbf_lookup_shadow_hits", &g_cbf_shadow_hits, kOptReadOnly, kAny},
     {"cms_running_fast", &g_running_fast, kOptReadOnly, kAny},
     {"cms_running_sequential", &g_running_sequential, kOptReadOnly, kAny},
+    {"cms_update_running_fast", &g_update_running_fast, kOptReadOnly, kAny},
+    {"cms_update_running_sequential", &g_update_running_sequential, kOptReadOnly, kAny},
     // measuring tools (bench builds only)
     {"part_debug", &g_part_debug, kOptKnob, kAny},
 };

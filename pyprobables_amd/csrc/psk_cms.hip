@@ -134,15 +134,18 @@ extern "C" int psk_cms_update_ordered(psk_sketch *s, int layout, const void *dat
 // countminsketch.py:267-288 for a whole ordered batch of adds: the table, elements_added and EVERY op's return value as the reference's loop
 // leaves them.  The parallel passes of psk_running.hpp wherever they apply (depth <= kMaxDepthMeanMin, width <= 2^32; weights >= 0 is the
 // entry's contract), else k_cms_ordered: always exact.  Which one ran: read-only options "cms_running_fast" / "cms_running_sequential".
-extern "C" int psk_cms_add_running(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len,
-                                   const int32_t *weights, int where, int query, int64_t els_in, void *out, int64_t *els_out, void *stream)
+// SGN: psk_cms_update_running, :267-321 -- a negative weight removes; the same chunking, eligibility and fall-back with the signed passes,
+// counted by "cms_update_running_fast" / "cms_update_running_sequential".
+template <bool SGN>
+static int cms_running(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, const int32_t *weights, int where,
+                       int query, int64_t els_in, void *out, int64_t *els_out, void *stream)
 {
     CHECK_HANDLE(s, PSK_KIND_CMS);
     PSK_TRY(check_hashes_width(s, layout, key_len));
     if (query < PSK_Q_MIN || query > PSK_Q_MEANMIN) return fail(PSK_EINVAL, "bad query %d", query);
     if (query == PSK_Q_MEANMIN && s->m < 2) return fail(PSK_EINVAL, "mean-min query needs width >= 2");
     if (n && !out) return fail(PSK_EINVAL, "out is NULL");
-    if (where == PSK_HOST && weights)
+    if (!SGN && where == PSK_HOST && weights)
         for (uint64_t i = 0; i < n; ++i)
             if (weights[i] < 0) return fail(PSK_EINVAL, "ordered add: weight %d of op %llu is negative", weights[i], (unsigned long long)i);
     hipStream_t st = (hipStream_t)stream;
@@ -165,9 +168,9 @@ extern "C" int psk_cms_add_running(psk_sketch *s, int layout, const void *data, 
     PSK_TRY(ensure(s->s_aux, 8ULL * (s->k > (uint32_t)kMaxDepthMeanMin ? s->k : 1u) + 8));
     int64_t *els_dev = where == PSK_DEVICE && els_out ? els_out : (int64_t *)s->s_aux.p;
     if (s->k <= (uint32_t)kMaxDepthMeanMin && s->m <= (1ULL << 32)) {
-        __atomic_add_fetch(&g_running_fast, 1, __ATOMIC_RELAXED);
+        __atomic_add_fetch(SGN ? &g_update_running_fast : &g_running_fast, 1, __ATOMIC_RELAXED);
         RunArena a;
-        PSK_TRY(cms_running_arena(s, n, &a));
+        PSK_TRY(cms_running_arena(s, n, &a, SGN));
         for (uint64_t base = 0; base < n; base += a.cap) {
             const uint32_t nc = (uint32_t)(n - base < a.cap ? n - base : a.cap);
             PSK_TRY(with_source(b, [&](auto src) {
@@ -177,10 +180,10 @@ extern "C" int psk_cms_add_running(psk_sketch *s, int layout, const void *data, 
                     return (int)PSK_OK;
                 });
             }));
-            PSK_TRY(cms_running_chunk(s, a, w, base, nc, base == 0, els_in, query, o.dev, els_dev, st));
+            PSK_TRY((SGN ? cms_running_chunk_signed : cms_running_chunk)(s, a, w, base, nc, base == 0, els_in, query, o.dev, els_dev, st));
         }
     } else {  // one lane, one op after the other (int64 weights and results: widened / narrowed around it)
-        __atomic_add_fetch(&g_running_sequential, 1, __ATOMIC_RELAXED);
+        __atomic_add_fetch(SGN ? &g_update_running_sequential : &g_running_sequential, 1, __ATOMIC_RELAXED);
         int64_t *wide = nullptr;
         if (s->k > (uint32_t)kMaxDepthMeanMin) wide = (int64_t *)s->s_aux.p + 1;
         PSK_TRY(ensure(s->s_perm, 8 * (n + 1)));
@@ -192,7 +195,7 @@ extern "C" int psk_cms_add_running(psk_sketch *s, int layout, const void *data, 
         }
         PSK_TRY(with_source(b, [&](auto src) {
             return with_pow2(s, [&](auto P) {
-                hipLaunchKernelGGL((k_cms_ordered<decltype(src), P.value>), dim3(1), dim3(64), 0, st, src, (int32_t *)s->table, s->md, s->k, w64, (int)PSK_OP_ADD, query,
+                hipLaunchKernelGGL((k_cms_ordered<decltype(src), P.value>), dim3(1), dim3(64), 0, st, src, (int32_t *)s->table, s->md, s->k, w64, (int)(SGN ? PSK_OP_SIGNED : PSK_OP_ADD), query,
                                    els_in, n, (int64_t *)s->s_perm.p, s->ctr, wide, (uint32_t *)nullptr, 0u);
                 HIP_TRY(hipGetLastError());
                 return (int)PSK_OK;
@@ -203,4 +206,16 @@ extern "C" int psk_cms_add_running(psk_sketch *s, int layout, const void *data, 
     }
     if (where == PSK_HOST && els_out) HIP_TRY(hipMemcpyAsync(els_out, els_dev, 8, hipMemcpyDeviceToHost, st));
     return finish(where, &o, st);
+}
+
+extern "C" int psk_cms_add_running(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len,
+                                   const int32_t *weights, int where, int query, int64_t els_in, void *out, int64_t *els_out, void *stream)
+{
+    return cms_running<false>(s, layout, data, offsets, n, key_len, weights, where, query, els_in, out, els_out, stream);
+}
+
+extern "C" int psk_cms_update_running(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len,
+                                      const int32_t *weights, int where, int query, int64_t els_in, void *out, int64_t *els_out, void *stream)
+{
+    return cms_running<true>(s, layout, data, offsets, n, key_len, weights, where, query, els_in, out, els_out, stream);
 }

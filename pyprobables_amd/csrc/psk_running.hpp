@@ -1,4 +1,5 @@
-// psk_running.hpp -- exact ORDERED CountMinSketch add with every op's return value, in parallel (psk_cms_add_running).
+// psk_running.hpp -- exact ORDERED CountMinSketch add with every op's return value, in parallel (psk_cms_add_running); signed batches
+// (adds and removes, psk_cms_update_running): the second half of this file.
 //
 // What the reference computes (countminsketch.py:267-288), one op after the other:
 //     for s < depth:  bin = T[s][h_s(key_i) % width] = min(bin + w_i, INT32_MAX)        value_s(i) = that bin
@@ -329,19 +330,11 @@ static __global__ __launch_bounds__(kRunSegBlock) void k_run_seg_commit(const ui
 }
 
 // ------------------------------------------------------------------ query
-// out[base + i] = query over the depth values of op i (the expressions of k_cms_ordered); WIDE: int64 results (mean-min), else int32
-template <bool WIDE>
-__global__ __launch_bounds__(kRunSegBlock) void k_run_query(const int32_t *run, const int32_t *w, const unsigned long long *tsum, const long long *st,
-                                                            uint64_t base, uint32_t n, uint32_t cap, uint32_t depth, uint64_t width, int query, void *out)
+// the query over the depth values of op i (the expressions of k_cms_ordered); els_of(): elements_added after the op, which only a mean-min
+// query with a non-zero value asks for
+template <class ElsOf>
+__device__ __forceinline__ int64_t run_query_value(const int32_t *run, uint32_t i, uint32_t cap, uint32_t depth, uint64_t width, int query, ElsOf els_of)
 {
-    __shared__ unsigned long long wtot[kRunSegBlock / 64];
-    const uint32_t i = blockIdx.x * kRunSegBlock + threadIdx.x;
-    unsigned long long pre = 0;
-    if (WIDE) {  // (uniform) elements_added after the op: only the mean-min query looks at it
-        const unsigned long long x = i < n ? run_weight(w, base + i) : 0u;
-        pre = tsum[blockIdx.x] + run_block_scan<kRunSegBlock>(x, wtot);
-    }
-    if (i >= n) return;
     int64_t r;
     if (query == 2) {  // mean-min :438-453
         int64_t vals[kMaxDepthMeanMin];
@@ -352,8 +345,7 @@ __global__ __launch_bounds__(kRunSegBlock) void k_run_query(const int32_t *run, 
         }
         if (all_zero) r = 0;  // (sorted: first and last zero <=> all zero)
         else {
-            long long els;
-            if (__builtin_saddll_overflow(st[1], (long long)pre, &els)) els = INT64_MAX;
+            const long long els = els_of();
             for (uint32_t s = 0; s < depth; ++s) vals[s] = vals[s] - floordiv((int64_t)els - vals[s], (int64_t)width - 1);
             sort_small(vals, depth);
             r = (depth % 2 == 0) ? floordiv(vals[depth / 2] + vals[depth / 2 - 1], 2) : vals[depth / 2];
@@ -367,6 +359,27 @@ __global__ __launch_bounds__(kRunSegBlock) void k_run_query(const int32_t *run, 
         }
         r = query == 1 ? floordiv(sum, (int64_t)depth) : mn;  // mean :434-436 / min :429-432
     }
+    return r;
+}
+
+// out[base + i] = query over the depth values of op i; WIDE: int64 results (mean-min), else int32
+template <bool WIDE>
+__global__ __launch_bounds__(kRunSegBlock) void k_run_query(const int32_t *run, const int32_t *w, const unsigned long long *tsum, const long long *st,
+                                                            uint64_t base, uint32_t n, uint32_t cap, uint32_t depth, uint64_t width, int query, void *out)
+{
+    __shared__ unsigned long long wtot[kRunSegBlock / 64];
+    const uint32_t i = blockIdx.x * kRunSegBlock + threadIdx.x;
+    unsigned long long pre = 0;
+    if (WIDE) {  // (uniform) elements_added after the op: only the mean-min query looks at it
+        const unsigned long long x = i < n ? run_weight(w, base + i) : 0u;
+        pre = tsum[blockIdx.x] + run_block_scan<kRunSegBlock>(x, wtot);
+    }
+    if (i >= n) return;
+    const int64_t r = run_query_value(run, i, cap, depth, width, query, [&]() {
+        long long els;
+        if (__builtin_saddll_overflow(st[1], (long long)pre, &els)) els = INT64_MAX;
+        return els;
+    });
     if (WIDE) ((int64_t *)out)[base + i] = r;
     else ((int32_t *)out)[base + i] = (int32_t)r;
 }
@@ -388,6 +401,229 @@ static __global__ __launch_bounds__(kBlock) void k_run_widen(const int32_t *w, u
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) out[i] = w[i];
 }
 
+// ================================================================== signed batches (psk_cms_update_running)
+// w >= 0 adds w, w < 0 removes -w (countminsketch.py:267-321).  A bin may now fall as well as rise, so "one saturating sum" no longer
+// describes it; what does is the op itself as a map.  Every op on a bin is x -> clamp(x + w, INT32_MIN, INT32_MAX) (add_alt clamps above
+// only, remove_alt below only; the value in front of the op lies inside the rails, so the full clamp describes both), and maps of the form
+//     (a, lo, hi):  x -> min(hi, max(lo, x + a))                                    lo <= hi
+// are closed under composition: (a1, lo1, hi1) followed by (a2, lo2, hi2) is
+//     (a1 + a2,  clamp(lo1 + a2, lo2, hi2),  clamp(hi1 + a2, lo2, hi2))
+// (clamping is monotone, so it distributes over the min / max of the first map).  Composition of functions is associative: the value of
+// a bin after op i is an inclusive segmented scan of MAPS in arrival order per (row, bin), applied to T0.  The hash, the stable sort and
+// the commit pass are those of the add path; the scan passes below are the counterparts of k_run_seg_reduce / _carry / _apply.
+// elements_added is the same thing on the int64 rails (:285-287, :317-319), not segmented.
+
+// One stretch of a sorted row as a map: that of its LAST segment as far as the stretch covers it; head = a segment starts inside it.
+// `a` is a plain sum: a chunk has at most 2^20 ops of |w| <= 2^31, so |a| <= 2^51 and int64 holds it without saturation; lo / hi are
+// values a bin can take, int32.
+struct RunMap {
+    int64_t a;
+    int32_t lo, hi;
+    uint32_t head;
+    static __device__ __forceinline__ RunMap identity() { return RunMap{0, INT32_MIN, INT32_MAX, 0u}; }  // (the identity on the values a bin can hold)
+    static __device__ __forceinline__ RunMap of(int32_t w, bool head) { return RunMap{w, INT32_MIN, INT32_MAX, head ? 1u : 0u}; }
+    __device__ __forceinline__ int32_t clamp(int64_t x) const { return (int32_t)(x < lo ? lo : (x > hi ? hi : x)); }
+    __device__ __forceinline__ int32_t operator()(int32_t x) const { return clamp((int64_t)x + a); }
+    // b follows a
+    static __device__ __forceinline__ RunMap combine(const RunMap &a, const RunMap &b)
+    {
+        if (b.head) return RunMap{b.a, b.lo, b.hi, 1u};
+        return RunMap{a.a + b.a, b.clamp((int64_t)a.lo + b.a), b.clamp((int64_t)a.hi + b.a), a.head};
+    }
+    static __device__ __forceinline__ RunMap shfl_up(const RunMap &x, int o)
+    {
+        return RunMap{(int64_t)__shfl_up((long long)x.a, o), __shfl_up(x.lo, o), __shfl_up(x.hi, o), (uint32_t)__shfl_up((int)x.head, o)};
+    }
+};
+
+__device__ __forceinline__ long long run_sat_add64(long long a, long long b)
+{
+    long long s;
+    if (__builtin_saddll_overflow(a, b, &s)) s = b > 0 ? INT64_MAX : INT64_MIN;
+    return s;
+}
+
+// The same map on the int64 rails, for elements_added.  `a` as above (a tile, a chunk: |a| <= 2^51); lo + a may leave int64 and saturates,
+// which the clamp that follows cannot tell from the true sum.
+struct RunMap64 {
+    long long a, lo, hi;
+    static __device__ __forceinline__ RunMap64 identity() { return RunMap64{0, INT64_MIN, INT64_MAX}; }
+    static __device__ __forceinline__ RunMap64 of(int32_t w) { return RunMap64{w, INT64_MIN, INT64_MAX}; }
+    __device__ __forceinline__ long long clamp(long long x) const { return x < lo ? lo : (x > hi ? hi : x); }
+    __device__ __forceinline__ long long operator()(long long x) const { return clamp(run_sat_add64(x, a)); }
+    static __device__ __forceinline__ RunMap64 combine(const RunMap64 &a, const RunMap64 &b)
+    {
+        return RunMap64{a.a + b.a, b.clamp(run_sat_add64(a.lo, b.a)), b.clamp(run_sat_add64(a.hi, b.a))};
+    }
+    static __device__ __forceinline__ RunMap64 shfl_up(const RunMap64 &x, int o) { return RunMap64{__shfl_up(x.a, o), __shfl_up(x.lo, o), __shfl_up(x.hi, o)}; }
+};
+
+// inclusive scan of one map per thread over a workgroup of NT threads (run_block_segscan for M = RunMap / RunMap64); `wtot`: NT / 64 entries
+template <int NT, class M>
+__device__ __forceinline__ M run_block_mapscan(M x, M *wtot)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const M y = M::shfl_up(x, o);
+        if (lane >= (uint32_t)o) x = M::combine(y, x);
+    }
+    if (lane == 63u) wtot[wave] = x;
+    __syncthreads();
+    M c = M::identity();
+    for (uint32_t u = 0; u < wave; ++u) c = M::combine(c, wtot[u]);
+    __syncthreads();  // (wtot may be reused by the caller)
+    return M::combine(c, x);
+}
+
+// the signed weight of op i of the batch (nullptr: +1); every int32 is valid, INT32_MIN removes 2^31
+__device__ __forceinline__ int32_t run_sweight(const int32_t *w, uint64_t i) { return w ? w[i] : 1; }
+
+// ------------------------------------------------------------------ elements_added
+// a 256-op tile of the batch as a map on elements_added, and the sum of its |w|
+struct RunTile {
+    RunMap64 f;
+    unsigned long long abs;
+};
+static __global__ __launch_bounds__(kRunSegBlock) void k_run_stile(const int32_t *w, uint64_t base, uint32_t n, RunTile *tile)
+{
+    __shared__ RunMap64 wtot[kRunSegBlock / 64];
+    __shared__ unsigned long long atot[kRunSegBlock / 64];
+    const uint32_t i = blockIdx.x * kRunSegBlock + threadIdx.x;
+    const int32_t x = i < n ? run_sweight(w, base + i) : 0;
+    const RunMap64 incl = run_block_mapscan<kRunSegBlock>(RunMap64::of(x), wtot);
+    const unsigned long long ab = run_block_scan<kRunSegBlock>((unsigned long long)(x < 0 ? -(long long)x : (long long)x), atot);
+    if (threadIdx.x == kRunSegBlock - 1) tile[blockIdx.x] = RunTile{incl, ab};
+}
+
+// ONE workgroup: els[t] = elements_added in front of tile t; st[1] = in front of the chunk, st[0] = behind it (both rails, per op:
+// countminsketch.py:285-287, :317-319); the handle's counters follow as k_cms_ordered leaves them (ctr[5] = elements_added, ctr[4] += sum |w|)
+static __global__ __launch_bounds__(kRunScanThreads) void k_run_stile_scan(const RunTile *tile, uint32_t ntiles, long long *els, long long *st, long long els_in,
+                                                                          int first, long long *ctr, long long *els_out)
+{
+    __shared__ RunMap64 wtot[kRunScanThreads / 64];
+    __shared__ unsigned long long atot[kRunScanThreads / 64];
+    __shared__ RunMap64 all[kRunScanThreads];
+    const uint32_t per = (ntiles + kRunScanThreads - 1) / kRunScanThreads;
+    const uint32_t lo = threadIdx.x * per < ntiles ? threadIdx.x * per : ntiles, hi = lo + per < ntiles ? lo + per : ntiles;
+    RunMap64 mine = RunMap64::identity();
+    unsigned long long ab = 0;
+    for (uint32_t t = lo; t < hi; ++t) {
+        mine = RunMap64::combine(mine, tile[t].f);
+        ab += tile[t].abs;
+    }
+    const RunMap64 incl = run_block_mapscan<kRunScanThreads>(mine, wtot);
+    const unsigned long long abs_all = run_block_scan<kRunScanThreads>(ab, atot);  // (< 2^52)
+    all[threadIdx.x] = incl;
+    __syncthreads();
+    const long long start = first ? els_in : st[0];
+    RunMap64 run = threadIdx.x ? all[threadIdx.x - 1] : RunMap64::identity();
+    for (uint32_t t = lo; t < hi; ++t) {
+        els[t] = run(start);
+        run = RunMap64::combine(run, tile[t].f);
+    }
+    __syncthreads();  // every thread has read st[0]
+    if (threadIdx.x == kRunScanThreads - 1) {
+        const long long end = incl(start);
+        st[1] = start;
+        st[0] = end;
+        ctr[5] = end;
+        if (els_out) *els_out = end;
+        const unsigned long long nb = (unsigned long long)ctr[4] + abs_all;
+        ctr[4] = (nb < (unsigned long long)ctr[4] || nb > (1ULL << 62)) ? (1LL << 62) : (long long)nb;
+    }
+}
+
+// ------------------------------------------------------------------ segmented scan of maps along a sorted row
+struct RunSElem {
+    uint32_t bin, op;
+    int32_t w;
+    bool valid, head;
+};
+// this thread's element of block blockIdx.x, row blockIdx.y; past the end: an identity segment of its own
+__device__ __forceinline__ RunSElem run_sseg_load(const uint2 *sorted, const int32_t *w, uint64_t base, uint32_t n, uint32_t cap)
+{
+    const uint32_t i = blockIdx.x * kRunSegBlock + threadIdx.x;
+    RunSElem e{0u, 0u, 0, i < n, true};
+    if (e.valid) {
+        const uint2 *row = sorted + (size_t)blockIdx.y * cap;
+        const uint2 p = row[i];
+        e.bin = p.x;
+        e.op = p.y;
+        e.head = i == 0 || row[i - 1].x != p.x;
+        e.w = run_sweight(w, base + p.y);
+    }
+    return e;
+}
+
+// agg[row * nblk + block] = the block as one RunMap
+static __global__ __launch_bounds__(kRunSegBlock) void k_run_sseg_reduce(const uint2 *sorted, const int32_t *w, uint64_t base, uint32_t n, uint32_t cap,
+                                                                        uint32_t nblk, RunMap *agg)
+{
+    __shared__ RunMap wtot[kRunSegBlock / 64];
+    const RunSElem e = run_sseg_load(sorted, w, base, n, cap);
+    const RunMap incl = run_block_mapscan<kRunSegBlock>(RunMap::of(e.w, e.head), wtot);
+    if (threadIdx.x == kRunSegBlock - 1) agg[(size_t)blockIdx.y * nblk + blockIdx.x] = incl;
+}
+
+// agg[row][b] -> what lies in front of block b (exclusive scan, in place); one workgroup per row
+static __global__ __launch_bounds__(kRunScanThreads) void k_run_sseg_carry(RunMap *agg, uint32_t nblk)
+{
+    __shared__ RunMap wtot[kRunScanThreads / 64];
+    __shared__ RunMap all[kRunScanThreads];
+    RunMap *a = agg + (size_t)blockIdx.x * nblk;
+    const uint32_t per = (nblk + kRunScanThreads - 1) / kRunScanThreads;
+    const uint32_t lo = threadIdx.x * per < nblk ? threadIdx.x * per : nblk, hi = lo + per < nblk ? lo + per : nblk;
+    RunMap mine = RunMap::identity();
+    for (uint32_t t = lo; t < hi; ++t) mine = RunMap::combine(mine, a[t]);
+    all[threadIdx.x] = run_block_mapscan<kRunScanThreads>(mine, wtot);
+    __syncthreads();
+    RunMap run = threadIdx.x ? all[threadIdx.x - 1] : RunMap::identity();
+    for (uint32_t t = lo; t < hi; ++t) {
+        const RunMap x = a[t];
+        a[t] = run;
+        run = RunMap::combine(run, x);
+    }
+}
+
+// run[row * cap + op] = the bin's value after the op (countminsketch.py:276-282, :309-314); an op whose unclamped prev + w lies outside
+// the rails -> ctr[PSK_CTR_SATURATED], the test of k_cms_ordered (a remove that lands exactly on INT32_MIN is no clamp)
+static __global__ __launch_bounds__(kRunSegBlock) void k_run_sseg_apply(const uint2 *sorted, const int32_t *w, uint64_t base, uint32_t n, uint32_t cap, uint32_t nblk,
+                                                                       const RunMap *carry, const int32_t *table, uint64_t width, int32_t *run, long long *ctr)
+{
+    __shared__ RunMap wtot[kRunSegBlock / 64];
+    __shared__ RunMap incl_s[kRunSegBlock];
+    const RunSElem e = run_sseg_load(sorted, w, base, n, cap);
+    const RunMap front = carry[(size_t)blockIdx.y * nblk + blockIdx.x];
+    incl_s[threadIdx.x] = RunMap::combine(front, run_block_mapscan<kRunSegBlock>(RunMap::of(e.w, e.head), wtot));
+    __syncthreads();
+    bool clamped = false;
+    if (e.valid) {
+        const RunMap before = e.head ? RunMap::identity() : (threadIdx.x ? incl_s[threadIdx.x - 1] : front);  // the bin's ops in front of this one
+        const int64_t cur = (int64_t)before(table[(uint64_t)blockIdx.y * width + e.bin]) + (int64_t)e.w;
+        clamped = cur > INT32_MAX || cur < INT32_MIN;
+        run[(size_t)blockIdx.y * cap + e.op] = (int32_t)(cur > INT32_MAX ? INT32_MAX : (cur < INT32_MIN ? INT32_MIN : cur));
+    }
+    const unsigned long long c = __ballot(clamped);
+    if ((threadIdx.x & 63u) == 0 && c) atomicAdd((unsigned long long *)(ctr + 3), (unsigned long long)__popcll(c));
+}
+
+// ------------------------------------------------------------------ query
+// k_run_query with the signed prefix: els[tile] = elements_added in front of the tile, the ops of the tile applied to it one map after the other
+template <bool WIDE>
+__global__ __launch_bounds__(kRunSegBlock) void k_run_squery(const int32_t *run, const int32_t *w, const long long *els, uint64_t base, uint32_t n, uint32_t cap,
+                                                             uint32_t depth, uint64_t width, int query, void *out)
+{
+    __shared__ RunMap64 wtot[kRunSegBlock / 64];
+    const uint32_t i = blockIdx.x * kRunSegBlock + threadIdx.x;
+    RunMap64 pre = RunMap64::identity();
+    if (WIDE) pre = run_block_mapscan<kRunSegBlock>(RunMap64::of(i < n ? run_sweight(w, base + i) : 0), wtot);  // (uniform)
+    if (i >= n) return;
+    const int64_t r = run_query_value(run, i, cap, depth, width, query, [&]() { return pre(els[blockIdx.x]); });
+    if (WIDE) ((int64_t *)out)[base + i] = r;
+    else ((int32_t *)out)[base + i] = (int32_t)r;
+}
+
 }  // namespace psk
 
 // ------------------------------------------------------------------ host side (psk_running.hip; the hash launch is psk_capi.hip's)
@@ -400,11 +636,16 @@ struct RunArena {
     int32_t *run;                 // [depth][cap]   value of row s after op i
     uint32_t *hist;               // [depth][256][tiles]
     psk::RunSeg *agg;             // [depth][blocks]
-    unsigned long long *tsum;     // [blocks]
+    unsigned long long *tsum;     // [blocks]       (signed batches: elements_added in front of every tile, as int64)
     long long *st;                // [0] elements_added behind the chunk in hand, [1] in front of it
+    psk::RunMap *magg;            // [depth][blocks]  signed batches only: the block aggregates as maps, in place of agg
+    psk::RunTile *tile;           // [blocks]         signed batches only
 };
-// sizes the arena for a batch of n ops and grows the scratch
-__attribute__((visibility("hidden"))) int cms_running_arena(psk_sketch *s, uint64_t n, RunArena *a);
+// sizes the arena for a batch of n ops and grows the scratch; sgn: a signed batch (magg and tile in place of agg)
+__attribute__((visibility("hidden"))) int cms_running_arena(psk_sketch *s, uint64_t n, RunArena *a, bool sgn = false);
 // everything behind the hash kernel for the chunk [base, base + n) of the batch: a.bins is filled; w / out are the BATCH's arrays
 __attribute__((visibility("hidden"))) int cms_running_chunk(psk_sketch *s, const RunArena &a, const int32_t *w, uint64_t base, uint32_t n, bool first,
                                                             int64_t els_in, int query, void *out, int64_t *els_out, hipStream_t st);
+// the same for a chunk of a signed batch (arena sized with sgn = true)
+__attribute__((visibility("hidden"))) int cms_running_chunk_signed(psk_sketch *s, const RunArena &a, const int32_t *w, uint64_t base, uint32_t n, bool first,
+                                                                   int64_t els_in, int query, void *out, int64_t *els_out, hipStream_t st);

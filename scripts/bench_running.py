@@ -7,7 +7,11 @@
   * StreamThreshold.add_many end to end, the host's dict work included, on the skewed stream.
 
 Warm-up first, then the median of `--reps` runs, each timed around a device synchronise.  `--trace`: a few ordered adds only, for a
-kernel-trace profiler run of its own.  One JSON line at the end."""
+kernel-trace profiler run of its own.  One JSON line at the end.
+
+`--signed`: the signed batches alone (update_many_ordered -> psk_cms_update_running), 2^20 ops into 2^20 x 5 with unit weights, half of
+them removes, over uniform keys and over one hot key; add_many_ordered on the same keys beside them; update_ordered (the one-lane kernel)
+over a prefix of 2^16 ops of the same signed streams, as a rate, and the ratio of the rates."""
 import argparse
 import json
 import statistics
@@ -25,6 +29,7 @@ import pyprobables_amd as pa  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--trace", action="store_true")
+ap.add_argument("--signed", action="store_true")
 args = ap.parse_args()
 
 WIDTH, DEPTH = 1 << 20, 5
@@ -76,6 +81,26 @@ def report(label, n, t):
     out[f"{label} n={n}"] = {"ms": med * 1e3, "min_ms": lo * 1e3, "max_ms": hi * 1e3, "mops": n / med / 1e6}
     return med
 
+
+if args.signed:
+    n, prefix = SIZES[0], 1 << 16
+    g = torch.Generator(device="cuda")
+    g.manual_seed(0x5EED)
+    signs = torch.randint(0, 2, (n,), device="cuda", generator=g, dtype=torch.int32) * 2 - 1  # +1 / -1, half of each
+    streams = (("uniform keys", distinct[:n]), ("one hot key", distinct[:1].expand(n, -1).contiguous()))
+    for name, keys in streams:
+        t_add = report(f"add_many_ordered, {name}", n, median_time(lambda: cms.add_many_ordered(keys), args.reps, before=cms.clear))
+        t_upd = report(f"update_many_ordered, half removes, {name}", n, median_time(lambda: cms.update_many_ordered(keys, signs), args.reps, before=cms.clear))
+        hk, hw = keys[:prefix].cpu().numpy(), signs[:prefix].cpu().numpy().astype("int64")
+        cms.clear()
+        cms.update_ordered(hk[:1000], hw[:1000])
+        t_seq = report(f"update_ordered (one-lane kernel), {name}", prefix, median_time(lambda: cms.update_ordered(hk, hw), 2, warm=0, before=cms.clear))
+        ratio = (n / t_upd) / (prefix / t_seq)
+        out[f"ratio_update_many_ordered_over_update_ordered, {name}"] = ratio
+        out[f"ratio_update_many_ordered_over_add_many_ordered, {name}"] = t_add / t_upd
+        print(f"{name}: update_many_ordered runs {ratio:.1f} x the rate of update_ordered, {t_add / t_upd:.2f} x the rate of add_many_ordered", flush=True)
+    print(json.dumps(out))
+    sys.exit(0)
 
 for n in SIZES:
     for label, keys in (("add_many_ordered distinct", distinct[:n]), ("add_many_ordered skewed", hot[:n])):
