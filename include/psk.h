@@ -86,6 +86,7 @@ enum psk_counter {
     PSK_CTR_VIOLATIONS = 2, /* unordered batch ops whose result depended on order (CBF partial/underflowing remove) */
     PSK_CTR_SATURATED = 3,  /* counter updates that hit a rail (UINT32_MAX / INT32_MAX / INT32_MIN) */
     PSK_CTR_ABS_BOUND = 4,  /* upper bound on |any counter| (selects the wrap-free fast path) */
+    PSK_CTR_SPILLED = 7,    /* diagnostic: probes of the last Bloom insert behind a clear that took pass 1's exact fallback (full bin / full segment) */
     PSK_CTR_COUNT = 8
 };
 

@@ -21,7 +21,7 @@ HOST, DEVICE, DEVICE_BORROWED = 0, 1, 2
 KEYS_FIXED, KEYS_VARLEN8, KEYS_VARLEN32, KEYS_HASHES = 0, 1, 2, 3
 Q_MIN, Q_MEAN, Q_MEANMIN = 0, 1, 2
 OP_ADD, OP_REMOVE, OP_SIGNED = 0, 1, 2
-CTR_ADDED, CTR_REMOVED, CTR_VIOLATIONS, CTR_SATURATED, CTR_ABS_BOUND, CTR_ELS_OUT, CTR_COUNT = 0, 1, 2, 3, 4, 5, 8
+CTR_ADDED, CTR_REMOVED, CTR_VIOLATIONS, CTR_SATURATED, CTR_ABS_BOUND, CTR_ELS_OUT, CTR_SPILLED, CTR_COUNT = 0, 1, 2, 3, 4, 5, 7, 8
 
 # PSK_LIB_PATH lets a bench A/B two builds of the engine inside one process launch each (same GPU box)
 LIB_PATH = Path(os.environ.get("PSK_LIB_PATH") or (Path(__file__).resolve().parent / "csrc" / "libpsk_hip.so"))

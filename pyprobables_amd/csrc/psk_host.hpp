@@ -369,6 +369,9 @@ template <class Src, class Pay, int KT>
 struct bins_eligible {
     static constexpr bool value = pay_bins_ok<Pay>::value && KT <= 8 && src_fat512<Src>::value;  // (the 16- and 8-byte layouts)
 };
+#ifndef PSK_BINS_CARRY_GROUP
+#define PSK_BINS_CARRY_GROUP 1  // (A/B: scripts/build_variant.sh -DPSK_BINS_CARRY_GROUP=0 = the capacity of a tile's own load alone)
+#endif
 constexpr size_t kBinSlackWords = 8 + 16;  // behind the last bin: what the write-out's last group may read past a bin's end + the bench build's phase-profile slots
 struct BinsPlan {
     uint32_t tile, cap, stride, per_cu;
@@ -388,14 +391,20 @@ static bool bins_plan(const PartGeom *g, BinsPlan *p)
     const double mean = (double)p->tile * kk / (double)g->nbuckets;
     uint32_t cap = (uint32_t)(mean + kSigmas * __builtin_sqrt(mean) + 2.0);
     cap = (cap + 5) / 6 * 6;            // whole groups
-    p->cap = cap;
     // words between bins: 2 in front of the probes (word 1 = the counter), the probes, the slot a full bin's stores land on -- rounded up to
     // 2 (mod 4), so that neighbouring bins start two banks apart (slot r of ALL bins is what the lanes of a wave write at about the same time)
-    uint32_t stride = kBinHead + cap + 1;
-    while (stride % 4 != 2) ++stride;
-    p->stride = stride;
-    p->lds = ((size_t)g->nbuckets * stride + kBinSlackWords) * 4;
-    if (p->lds > kScatterLdsBudget / 2) return false;   // (at least two workgroups per CU, or the old shape does better)
+    auto plan = [&](uint32_t c) {   // fills *p only where the bins fit
+        uint32_t stride = kBinHead + c + 1;
+        while (stride % 4 != 2) ++stride;
+        const size_t lds = ((size_t)g->nbuckets * stride + kBinSlackWords) * 4;
+        if (lds > kScatterLdsBudget / 2) return false;   // (at least two workgroups per CU, or the old shape does better)
+        p->cap = c;
+        p->stride = stride;
+        p->lds = lds;
+        return true;
+    };
+    // a bin starts a tile with up to 5 probes it kept back from the tile before (k_part_bins): one more group, where the bins then still fit twice
+    if (!(PSK_BINS_CARRY_GROUP && plan(cap + 6)) && !plan(cap)) return false;
     uint32_t per_cu = (uint32_t)(kScatterLdsBudget / p->lds);
     const uint32_t by_waves = 2048u / (uint32_t)kBinThreads;   // (32 wave slots per CU)
     p->per_cu = per_cu > by_waves ? by_waves : per_cu;

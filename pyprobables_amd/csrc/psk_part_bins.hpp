@@ -12,10 +12,13 @@
 //   barrier
 //   write-out    slice b belongs to the SAME lanes in every tile (NT / B lanes per slice, or several slices per lane): they turn the bin
 //                into 16-byte groups (the probe format of PayNone / PayTileTag: 6 x 20 bits, counted halves), append them at a segment
-//                cursor kept in a REGISTER, and zero the bin's count;
+//                cursor kept in a REGISTER -- whole groups only: the up to five probes left over move to the front of the bin and leave with
+//                the next tile's (a workgroup runs ~13 tiles of a 10 M-key batch: one padded group per segment, written behind the last tile,
+//                instead of one per tile and slice -- 6 % of the probe stream were pad slots) --, and set the bin's count to what it kept;
 //   barrier
-// -- two barriers per tile, no scan, no second pass over the probes, no cursor / offset / delta arrays.  Same segments, same groups, same
-// segment counts as k_part_scatter: pass 2 (k_bloom_apply, k_bloom_test_flag, the nibble folds) does not know which pass 1 ran.
+// -- two barriers per tile, no scan, no second pass over the probes, no cursor / offset / delta arrays.  Same segments, same group format, same
+// segment counts as k_part_scatter, and the same probes in them: pass 2 (k_bloom_apply, k_bloom_test_flag, the nibble folds) does not know
+// which pass 1 ran.  (PayTileTag: a group's ordinal may be one ahead of a carried probe's tile, never more; k_bloom_test_flag flags both.)
 // Bins are `stride` words apart (cap rounded up to an even number + 2): consecutive bins start two banks apart, so that slot r of all
 // bins -- what the lanes of a wave write at about the same time -- does not sit in ONE bank.
 //
@@ -59,6 +62,23 @@ struct pay_bins_ok<PayWeightSmall> { static constexpr bool value = true; };  // 
 // them the FNV chains), so everything around the chains is counted in instructions: one v_bfe + one 24-bit multiply turn a hash into its bin's
 // byte offset, which is the address of the bin's counter AND (plus what the counter returns) of the probe's slot.
 constexpr uint32_t kBinHead = 2;  // words in front of a bin's probes
+// a group that holds nv < 6 probes (the first nv of the six slots a0 .. a2): the slots past the count read as pads -- all ones in the field, as
+// k_part_scatter leaves them (WP: the all-zero field) --, t0 / t1 = the tile's ordinal as PayTileTag spells it above the halves' counts
+template <bool WP>
+__device__ __forceinline__ uint4 bin_short_group(const uint2 a0, const uint2 a1, const uint2 a2, uint32_t nv, uint32_t mask, uint32_t t0, uint32_t t1)
+{
+    uint32_t f[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y};
+#pragma unroll
+    for (int x = 1; x < 6; ++x)
+        if ((uint32_t)x >= nv) f[x] = WP ? 0u : mask;
+    const uint32_t n0 = nv < 3u ? nv : 3u, n1 = nv - n0;
+    uint4 o;
+    o.x = f[0] | (f[1] << 20);
+    o.y = (f[1] >> 12) | (f[2] << 8) | ((n0 | t0) << 28);
+    o.z = f[3] | (f[4] << 20);
+    o.w = (f[4] >> 12) | (f[5] << 8) | ((n1 | t1) << 28);
+    return o;
+}
 template <class Src, class IdxFn, class Pay, class Spill, int KT, int KPT>
 __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src, IdxFn idxfn, Pay pay, Spill spill, PartGeom g, uint32_t n, uint32_t cap,
                                                               uint32_t stride, uint32_t *segcnt, uint4 *buckets)
@@ -85,12 +105,14 @@ __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src
     constexpr int kSlicesPerLane = kBinSlicesPerLane;
     const uint32_t sub = B <= (uint32_t)NT ? threadIdx.x % L : 0u;
     uint32_t myb[kSlicesPerLane], cur[kSlicesPerLane];
+    uint32_t carry[kSlicesPerLane];  // probes (< 6) my bin kept back from the tile before: they sit in its first slots and leave with the next whole group
     uint4 *seg[kSlicesPerLane];  // my segment of the slice (slot 0)
 #pragma unroll
     for (int s = 0; s < kSlicesPerLane; ++s) {
         myb[s] = B <= (uint32_t)NT ? (s == 0 && threadIdx.x / L < B ? threadIdx.x / L : ~0u) : threadIdx.x + (uint32_t)s * NT;
         if (myb[s] >= B) myb[s] = ~0u;
         cur[s] = 0;
+        carry[s] = 0;
         seg[s] = buckets + (seg_index(g, 0, blockIdx.x) + (myb[s] == ~0u ? 0u : myb[s])) * g.segcap;
     }
     for (uint32_t b = threadIdx.x; b < B; b += NT) *reinterpret_cast<uint32_t *>(lds + b * stride4 + kCnt) = kBinHead * 4u;
@@ -249,11 +271,16 @@ __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src
         for (int s = 0; s < kSlicesPerLane; ++s) {
             const uint32_t b = myb[s];
             if (b == ~0u) continue;
-            const char *bin = lds + b * stride4;
+            char *bin = lds + b * stride4;
             const uint32_t c4 = *reinterpret_cast<const uint32_t *>(bin + kCnt);
-            const uint32_t c = ((c4 < full4 ? c4 : full4) >> 2) - kBinHead;  // probes in the bin
-            const uint32_t whole = c / 6u, rem = c - 6u * whole, ngroups = whole + (rem ? 1u : 0u);
-            const uint2 *e = reinterpret_cast<const uint2 *>(bin + kBinHead * 4u);
+            const uint32_t c = ((c4 < full4 ? c4 : full4) >> 2) - kBinHead;  // probes in the bin, the carried ones in front
+            const uint32_t whole = c / 6u, rem = c - 6u * whole;
+            // Only whole groups leave; the remainder stays in the bin and joins the next tile's probes, so a segment is padded once, by the
+            // flush behind the tile loop, and not once per tile.  PayTileTag: a group of ordinal o may hold probes of tile o - 1 and of no
+            // older one (k_bloom_test_flag flags both), so a bin that was handed probes and is still short of a group sends them out now, padded
+            const bool tail = pay_tile_tag<Pay>::value && whole == 0 && carry[s] != 0;
+            const uint32_t ngroups = whole + (tail ? 1u : 0u);
+            uint2 *e = reinterpret_cast<uint2 *>(bin + kBinHead * 4u);
             uint4 *out = seg[s] + cur[s];
             if (cur[s] + ngroups <= g.segcap) {  // (all but never)
                 const uint32_t hi0 = (3u | t0) << 28, hi1 = (3u | t1) << 28;
@@ -266,54 +293,49 @@ __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src
                     o.w = (a2.x >> 12) | (a2.y << 8) | hi1;
                     if (!(dbg & 1)) out[gq] = o;
                 }
-                if (rem && sub == (whole & (L - 1))) {  // the run's last group: the slots past the count read as pads (all ones in the field, as k_part_scatter leaves them)
-                    const uint2 a0 = e[3 * whole], a1 = e[3 * whole + 1], a2 = e[3 * whole + 2];
-                    uint32_t f[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y};
-#pragma unroll
-                    for (int x = 1; x < 6; ++x)
-                        if ((uint32_t)x >= rem) f[x] = WP ? 0u : mask;
-                    const uint32_t n0 = rem < 3u ? rem : 3u, n1 = rem - n0;
-                    uint4 o;
-                    o.x = f[0] | (f[1] << 20);
-                    o.y = (f[1] >> 12) | (f[2] << 8) | ((n0 | t0) << 28);
-                    o.z = f[3] | (f[4] << 20);
-                    o.w = (f[4] >> 12) | (f[5] << 8) | ((n1 | t1) << 28);
-                    if (!(dbg & 1)) out[whole] = o;
+                if constexpr (pay_tile_tag<Pay>::value) {
+                    if (tail && sub == 0 && !(dbg & 1)) out[0] = bin_short_group<WP>(e[0], e[1], e[2], rem, mask, t0, t1);
                 }
-            } else {  // the segment fills up: group by group, what does not fit takes the exact fallback probe by probe
-                for (uint32_t gq = sub; gq < ngroups; gq += L) {
+                if (rem && whole && sub == (whole & (L - 1))) {  // the remainder moves to the bin's first slots (whole == 0: it is there)
+                    // the lanes that share a slice are neighbours in ONE wave, and a wave's LDS operations complete in order: these stores
+                    // stay behind every whole-group read of the bin above (the compiler must not move them up either)
+                    __builtin_amdgcn_wave_barrier();
+                    const uint2 a0 = e[3 * whole], a1 = e[3 * whole + 1], a2 = e[3 * whole + 2];
+                    e[0] = a0;
+                    e[1] = a1;
+                    e[2] = a2;
+                }
+                carry[s] = tail ? 0u : rem;
+                cur[s] += ngroups;
+            } else {  // the segment fills up: group by group, the remainder as a padded one; what does not fit takes the exact fallback probe by probe
+                const uint32_t nall = whole + (rem ? 1u : 0u);
+                for (uint32_t gq = sub; gq < nall; gq += L) {
                     const uint2 a0 = e[3 * gq], a1 = e[3 * gq + 1], a2 = e[3 * gq + 2];
-                    uint32_t f[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y};
                     const uint32_t left = c - 6u * gq, nv = left < 6u ? left : 6u;
-#pragma unroll
-                    for (int x = 1; x < 6; ++x)
-                        if ((uint32_t)x >= nv) f[x] = WP ? 0u : mask;
-                    const uint32_t n0 = nv < 3u ? nv : 3u, n1 = nv - n0;
                     if (cur[s] + gq < g.segcap) {
-                        uint4 o;
-                        o.x = f[0] | (f[1] << 20);
-                        o.y = (f[1] >> 12) | (f[2] << 8) | ((n0 | t0) << 28);
-                        o.z = f[3] | (f[4] << 20);
-                        o.w = (f[4] >> 12) | (f[5] << 8) | ((n1 | t1) << 28);
-                        out[gq] = o;
+                        out[gq] = bin_short_group<WP>(a0, a1, a2, nv, mask, t0, t1);
                     } else {
+                        const uint32_t f[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y};
 #pragma unroll
                         for (int x = 0; x < 6; ++x)
                             if ((uint32_t)x < nv) {
-                                if constexpr (pay_tile_tag<Pay>::value) spill((b << g.shift) | f[x], tile);
-                                else if constexpr (WP) spill((b << g.shift) | (f[x] & mask), f[x] >> 15);
+                                if constexpr (pay_tile_tag<Pay>::value) {  // (a carried probe is of the tile before: both are flagged)
+                                    spill((b << g.shift) | f[x], tile);
+                                    if (ordinal) spill((b << g.shift) | f[x], tile - gridDim.x);
+                                } else if constexpr (WP) spill((b << g.shift) | (f[x] & mask), f[x] >> 15);
                                 else spill((b << g.shift) | f[x], 0u);
                             }
                     }
                 }
+                carry[s] = 0;
+                cur[s] += nall;
             }
-            cur[s] += ngroups;
         }
         // (the lanes that share a slice are neighbours in ONE wave, and a wave's LDS operations complete in order: the counter is reset behind
-        // every read of it above)
+        // every read of it above; the next tile's probes go behind the carried ones)
 #pragma unroll
         for (int s = 0; s < kSlicesPerLane; ++s)
-            if (myb[s] != ~0u && sub == 0) *reinterpret_cast<uint32_t *>(lds + myb[s] * stride4 + kCnt) = kBinHead * 4u;
+            if (myb[s] != ~0u && sub == 0) *reinterpret_cast<uint32_t *>(lds + myb[s] * stride4 + kCnt) = (kBinHead + carry[s]) * 4u;
 #pragma unroll
         for (int q = 0; q < KPT; ++q) {
             Src::pin(kcur[q]);
@@ -322,6 +344,30 @@ __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src
         PSK_BIN_TICK(2);
         lds_barrier();
         PSK_BIN_TICK(3);
+    }
+    // ---- what my bins kept back from the last tile: each segment's one padded group (the barrier that ends the last tile is behind the move
+    // that put these probes in front)
+    if (ordinal != ~0u) {
+        const uint32_t t0 = pay_tile_tag<Pay>::value ? (ordinal & 3u) << 2 : 0u, t1 = pay_tile_tag<Pay>::value ? ordinal & 12u : 0u;
+#pragma unroll
+        for (int s = 0; s < kSlicesPerLane; ++s) {
+            if (myb[s] == ~0u || sub != 0 || carry[s] == 0) continue;
+            const uint2 *e = reinterpret_cast<const uint2 *>(lds + myb[s] * stride4 + kBinHead * 4u);
+            const uint2 a0 = e[0], a1 = e[1], a2 = e[2];
+            if (cur[s] < g.segcap) {
+                if (!(dbg & 1)) seg[s][cur[s]] = bin_short_group<WP>(a0, a1, a2, carry[s], mask, t0, t1);
+            } else {  // the segment is full: the exact fallback
+                const uint32_t f[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y};
+#pragma unroll
+                for (int x = 0; x < 6; ++x)
+                    if ((uint32_t)x < carry[s]) {
+                        if constexpr (pay_tile_tag<Pay>::value) spill((myb[s] << g.shift) | f[x], ordinal * gridDim.x + blockIdx.x);
+                        else if constexpr (WP) spill((myb[s] << g.shift) | (f[x] & mask), f[x] >> 15);
+                        else spill((myb[s] << g.shift) | f[x], 0u);
+                    }
+            }
+            cur[s] += 1;
+        }
     }
     if (t_lane) {  // (bench-only) behind the segment counts, where scripts/ablate.py reads them (psk_debug_phase_profile)
         unsigned long long *prof = reinterpret_cast<unsigned long long *>(segcnt + (size_t)g.nbuckets * g.nwg);
@@ -336,7 +382,8 @@ __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src
                 tally_a += __shfl_down(tally_a, o);
                 tally_b += __shfl_down(tally_b, o);
             }
-            unsigned long long *red = reinterpret_cast<unsigned long long *>(smem);  // (the tile loop is over: the bins are free)
+            lds_barrier();  // (the flush above has read the bins: they are free)
+            unsigned long long *red = reinterpret_cast<unsigned long long *>(smem);
             if ((threadIdx.x & 63) == 0) {
                 red[3 * (threadIdx.x >> 6)] = (unsigned long long)tally_s;
                 red[3 * (threadIdx.x >> 6) + 1] = tally_a;

@@ -2,6 +2,7 @@
 #include "psk_host.hpp"
 
 static_assert(kBloomApplyCtrWords == PSK_CTR_COUNT, "k_bloom_apply's store mode zeroes the whole counter block");
+static_assert(kBloomApplyCtrSpilled == PSK_CTR_SPILLED, "... and leaves the length of pass 1's spill list in this slot");
 
 // Bloom insert through the partitioned path; *done = false when this batch/table is not eligible
 int PSK_VARIANT(bloom_add_partitioned)(psk_sketch *s, const Batch &b, hipStream_t st, bool *done)

@@ -1479,6 +1479,7 @@ __device__ __forceinline__ void for_each_group_padded(const uint4 *buckets, cons
 // not bucket wait in spill (SpillBloomOr's list: [0] count, [1] workgroups done, [2 ..] bit indices); every workgroup ORs the entries
 // of its own slice into its image first (~10^3 entries per 10M keys), and the last workgroup to finish resets the two header words.
 constexpr uint32_t kBloomApplyCtrWords = 8;  // == PSK_CTR_COUNT (static_assert in psk_part_bloom_add.hip)
+constexpr uint32_t kBloomApplyCtrSpilled = 7;  // == PSK_CTR_SPILLED
 struct BloomApplyStore {
     uint32_t on = 0;
     const uint32_t *spill = nullptr;
@@ -1504,8 +1505,10 @@ static __global__ __launch_bounds__(kApplyThreads) void k_bloom_apply(uint32_t *
         if (nv > 2) { const uint32_t x = (uint32_t)(h >> 40) & 0xFFFFFu; atomicOr(&smem[x >> 5], 1u << (x & 31)); }
     };
     for_each_group(buckets, segcnt, g, b, make_uint4(0, 0, 0, 0), [&](const uint4 q) { half(q.x, q.y); half(q.z, q.w); });
+    uint32_t spilled = 0;  // (store mode) the length of pass 1's spill list: read ONCE, in front of the barrier the list's reset waits behind
     if (sm.on) {
-        const uint32_t nsp = sm.spill[0] < sm.spill_cap ? sm.spill[0] : sm.spill_cap;
+        spilled = sm.spill[0];
+        const uint32_t nsp = spilled < sm.spill_cap ? spilled : sm.spill_cap;
         const uint32_t lmask = (1u << g.shift) - 1u;
         for (uint32_t i = threadIdx.x; i < nsp; i += kApplyThreads) {
             const uint32_t x = sm.spill[2 + i];
@@ -1537,7 +1540,8 @@ static __global__ __launch_bounds__(kApplyThreads) void k_bloom_apply(uint32_t *
         }
         if (b == gridDim.x - 1)
             for (uint64_t gw = (uint64_t)gridDim.x * slice_words + threadIdx.x; gw < tab_words; gw += kApplyThreads) tab[gw] = 0;
-        if (b == 0 && threadIdx.x < kBloomApplyCtrWords) sm.ctr[threadIdx.x] = 0;
+        // (the counter block starts again; PSK_CTR_SPILLED = how many probes pass 1 handed to the list -- the count every lane read above)
+        if (b == 0 && threadIdx.x < kBloomApplyCtrWords) sm.ctr[threadIdx.x] = threadIdx.x == kBloomApplyCtrSpilled ? (long long)spilled : 0;
         if (threadIdx.x == 0) {  // every lane of this workgroup has read the count (the barrier above): the last workgroup resets the list
             uint32_t *hdr = const_cast<uint32_t *>(sm.spill);
             if (atomicAdd(hdr + 1, 1u) == gridDim.x - 1) {
@@ -1713,6 +1717,9 @@ static __global__ __launch_bounds__(kApplyThreads) void k_bloom_test_flag(const 
                 nmiss += (uint32_t)__builtin_popcount(clear);
                 const uint32_t ordinal = (q[d].y >> 30) | ((q[d].w >> 30) << 2);
                 tileflag[ordinal * g.nwg + wg[d]] = gen;
+                // (k_part_bins carries a bin's remainder into the next tile's first group: the probe may be of the tile before.  One tile
+                // flagged too many costs its re-check, nothing else: k_bloom_flag_resolve is exact)
+                if (ordinal) tileflag[(ordinal - 1u) * g.nwg + wg[d]] = gen;
                 tileflag[-1] = gen;  // "some tile of this round is flagged" (k_bloom_flag_resolve)
             }
         }
