@@ -326,7 +326,7 @@ int psk_digest_chain(int algo, int layout, const void *data, const uint64_t *off
  *   filter        remainders, uint8 / uint16 / uint32 per slot for r <= 8 / r <= 16 / else (the reference's array type codes B / I / L)
  *   occupied, continuation, shifted   bit arrays, LSB first in 32-bit words, max(2^q / 32, 1) words each
  * The reference drops duplicates and keeps runs sorted, so its table depends only on the SET of hashes inserted; every call below
- * produces or reads exactly that table (DESIGN.md "Quotient filter").  Removal (quotientfilter.py:168-185) is not offered.
+ * produces or reads exactly that table (DESIGN.md "Quotient filter").
  *   hash       out[i] = fnv_1a_32(key_i, 0) (hashes.py:106-122: add / check hash this way); `where` as everywhere (out follows the keys);
  *              PSK_KEYS_HASHES rows give the low 32 bits of their first hash
  *   build      the table of the n SORTED DISTINCT hashes (n <= 2^q; sorting and deduplicating is the caller's -- any radix sort), written
@@ -338,7 +338,13 @@ int psk_digest_chain(int algo, int layout, const void *data, const uint64_t *off
  *              bits and slots in use, marks_dev[0] the first slot with continuation = shifted = 0, marks_dev[1] the first empty slot
  *              (0xFFFFFFFF: full table; quotientfilter.py:215-218 starts hashes() there); the caller turns each row into INCLUSIVE
  *              prefix sums in place and calls again with out_dev (uint32[out_cap], out_cap >= the last entry of row 2: the element
- *              count) (quotientfilter.py:208-245 hashes / get_hashes).  Enqueue only. */
+ *              count) (quotientfilter.py:208-245 hashes / get_hashes).  Enqueue only.
+ *   remove_alt `for h in hashes: remove_alt(h)` (quotientfilter.py:177-185, _remove_element :396-469) for n SORTED DISTINCT device hashes, on a
+ *              table with at least one empty slot and q >= 5 (a smaller or a completely full table is rebuilt: decode, drop, build): the table
+ *              of the remaining set, repaired in place cluster by cluster (DESIGN.md "Quotient filter: removal"); absent hashes are no-ops.
+ *              scratch_dev: 2 * words + 2 + n uint32 whose first 2 * words + 2 are ZERO on entry and zero again when the call has run (one
+ *              allocation serves every call on the table); *removed_dev receives the number of hashes taken out.  The reference's
+ *              `_elements_added` is not decremented by a removal: that counter is the caller's.  Enqueue only. */
 int psk_qf_hash(int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, uint32_t *out,
                 int device, void *stream);
 int psk_qf_build(uint32_t q, const uint32_t *sorted_hashes_dev, uint64_t n, void *filter_dev, uint32_t *occupied_dev,
@@ -348,6 +354,8 @@ int psk_qf_check(uint32_t q, const void *filter_dev, const uint32_t *occupied_de
                  int where, uint8_t *out, int device, void *stream);
 int psk_qf_check_alt(uint32_t q, const void *filter_dev, const uint32_t *occupied_dev, const uint32_t *continuation_dev,
                      const uint32_t *shifted_dev, const uint32_t *hashes_dev, uint64_t n, uint8_t *out_dev, int device, void *stream);
+int psk_qf_remove_alt(uint32_t q, void *filter_dev, uint32_t *occupied_dev, uint32_t *continuation_dev, uint32_t *shifted_dev,
+                      const uint32_t *sorted_hashes_dev, uint64_t n, uint32_t *scratch_dev, uint32_t *removed_dev, int device, void *stream);
 int psk_qf_decode(uint32_t q, const void *filter_dev, const uint32_t *occupied_dev, const uint32_t *continuation_dev,
                   const uint32_t *shifted_dev, int64_t *word_counts_dev, uint32_t *marks_dev, uint32_t *out_dev, uint64_t out_cap,
                   int device, void *stream);

@@ -1,4 +1,4 @@
-// psk_quotient.hip -- quotient filter: bulk build, lookup of pre-computed hashes, decode (include/psk.h "QuotientFilter").
+// psk_quotient.hip -- quotient filter: bulk build, lookup of pre-computed hashes, batch removal in place, decode (include/psk.h "QuotientFilter").
 //
 // Build (k_qf_tile_max / k_qf_tile_scan / k_qf_place).  For the sorted distinct hashes h_0 < h_1 < ..., quotients q_i = h_i >> r, the
 // reference's table stores element i at
@@ -146,6 +146,128 @@ __global__ __launch_bounds__(kBlock) void k_qf_check_alt(psk::QfTable t, const u
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) out[i] = psk::qf_contains(t, hashes[i]) ? 1 : 0;
 }
 
+// ---- removal (psk_qf_remove_alt; q >= 5: a metadata word is 32 real slots)
+// A cluster is a slot with shifted = 0 in use and the shifted slots behind it.  Taking elements out moves the rest of THEIR cluster left and
+// nothing else: the next cluster's head sits in its own quotient's slot and stays there.  So launch 1 marks, launch 2 repairs each marked cluster
+// by itself, in place.
+//
+// k_qf_locate: one lane per hash, the lookup walk.  A hit sets its slot's bit in `dead`; the lane that sets the bit for the first time counts it
+// and sets the cluster start's bit in `dirty`, and the lane that sets THAT bit for the first time owns the cluster: it appends the start to `list`.
+__global__ __launch_bounds__(kBlock) void k_qf_locate(psk::QfTable t, const uint32_t *hashes, uint64_t n, uint32_t *dead, uint32_t *dirty, uint32_t *cursor,
+                                                      uint32_t *list, uint32_t *removed)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    uint32_t hits = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        uint32_t slot = 0, start = 0;
+        if (!psk::qf_find(t, hashes[i], slot, start)) continue;
+        const uint32_t bit = 1u << (slot & 31u);
+        if (atomicOr(dead + (slot >> 5), bit) & bit) continue;  // the same hash twice in the batch
+        ++hits;
+        const uint32_t sbit = 1u << (start & 31u);
+        if (atomicOr(dirty + (start >> 5), sbit) & sbit) continue;
+        const uint32_t at = atomicAdd(cursor, 1u);
+        if (at < n) list[at] = start;
+    }
+    for (int o = 32; o > 0; o >>= 1) hits += __shfl_xor(hits, o);
+    if ((threadIdx.x & 63) == 0 && hits) atomicAdd(removed, hits);
+}
+
+// k_qf_repack: one lane per listed cluster, start b.  The lane reads the cluster slot by slot (offset `steps` from b, modulo the table) up to the
+// first slot with shifted = 0 -- an empty slot or the next cluster's head -- and writes the survivors behind its read position:
+//     offset of a survivor = max(offset of its quotient, offset of the survivor before it + 1)        (the build's rule, restarted at b)
+// with continuation = "same run as the survivor before" and shifted = "not in its quotient's slot".  The k-th run of the cluster belongs to the
+// k-th set `occupied` bit from b (`oc` walks them); a run without survivors clears its bit.  Offsets no survivor took are zeroed in filter,
+// continuation and shifted: the tail the cluster gave up, and gaps -- a survivor that falls back to its own quotient's slot behind a gap heads a
+// cluster of its own, so a cluster may leave as several.  Nothing is written before the first dead slot (the slots in front of it keep their
+// place).  Writes never pass the read position (a survivor's old offset is >= its quotient's and >= the count of slots before it), and every bit
+// the lane reads ahead is one only this lane may change: quotients, slots, dead bits of [b, end) are the cluster's own.
+// Two clusters can share a metadata word, so bits are changed with atomicAnd / atomicOr on the word, gathered per word (`mw`); remainders are
+// plain stores.  The lane clears the dead bits it read and its dirty bit: the scratch goes back zeroed.
+// Bounds: every loop ends after at most `size` steps and every slot index is masked, so arrays that are no quotient filter's give some table, not
+// a spin or an access outside the arrays.
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_qf_repack(T *filter, uint32_t *occ, uint32_t *cont, uint32_t *sh, uint32_t q, uint32_t *dead, uint32_t *dirty,
+                                                      const uint32_t *cursor, const uint32_t *list, uint64_t cap)
+{
+    const uint32_t smask = (1u << q) - 1u, wmask = smask >> 5;
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t count = *cursor < cap ? *cursor : cap;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) {
+        const uint32_t b = list[i] & smask;
+        uint32_t mw = b >> 5, mmask = 0, mc = 0, ms = 0;  // the metadata word being written: bits decided, continuation and shifted values
+        auto flush = [&]() {
+            const uint32_t c0 = mmask & ~mc, s0 = mmask & ~ms;
+            if (c0) atomicAnd(cont + mw, ~c0);
+            if (mc) atomicOr(cont + mw, mc);
+            if (s0) atomicAnd(sh + mw, ~s0);
+            if (ms) atomicOr(sh + mw, ms);
+            mmask = mc = ms = 0;
+        };
+        auto emit = [&](uint32_t off, bool c, bool s, T rem) {  // offsets arrive ascending, each once
+            const uint32_t p = (b + off) & smask, bit = 1u << (p & 31u);
+            if ((p >> 5) != mw) {
+                flush();
+                mw = p >> 5;
+            }
+            mmask |= bit;
+            if (c) mc |= bit;
+            if (s) ms |= bit;
+            filter[p] = rem;
+        };
+        uint32_t rw = 0xFFFFFFFFu, wsh = 0, wcont = 0, wdead = 0, dbits = 0;  // the word being read, and the dead bits consumed in it
+        uint32_t oc = b, alive = 0;  // the quotient of the run being read, its survivors so far
+        uint32_t next = 0, eo = 0;   // the earliest offset the next survivor may take; the next offset to write
+        bool moved = false;          // a dead slot was met: from `eo` on the cluster is rewritten
+        bool sound = true;
+        uint32_t steps = 0;
+        for (; steps <= smask; ++steps) {
+            const uint32_t p = (b + steps) & smask, bit = 1u << (p & 31u);
+            if ((p >> 5) != rw) {
+                if (dbits) atomicAnd(dead + rw, ~dbits);
+                rw = p >> 5, dbits = 0;
+                wsh = sh[rw], wcont = cont[rw], wdead = dead[rw];
+            }
+            if (steps && !(wsh & bit)) break;
+            if (steps && !(wcont & bit)) {  // the next run starts here
+                if (!alive) atomicAnd(occ + (oc >> 5), ~(1u << (oc & 31u)));
+                alive = 0;
+                const uint32_t x = (oc + 1u) & smask;
+                uint32_t w = x >> 5, m = occ[w] & (0xFFFFFFFFu << (x & 31u));
+                for (uint32_t guard = 0; guard <= wmask && !m; ++guard) {
+                    w = (w + 1u) & wmask;
+                    m = occ[w];
+                }
+                if (!m) {  // more runs than occupied bits: not a quotient filter's table
+                    sound = false;
+                    break;
+                }
+                oc = (w << 5) + (uint32_t)__ffs(m) - 1u;
+            }
+            if (wdead & bit) {
+                dbits |= bit;
+                if (!moved) moved = true, eo = steps;
+                continue;
+            }
+            const uint32_t qo = (oc - b) & smask, wo = qo > next ? qo : next;
+            next = wo + 1u;
+            if (moved) {
+                const T rem = filter[p];
+                for (; eo < wo; ++eo) emit(eo, false, false, (T)0);
+                emit(wo, alive != 0, wo != qo, rem);
+                eo = wo + 1u;
+            }
+            ++alive;
+        }
+        if (sound && !alive) atomicAnd(occ + (oc >> 5), ~(1u << (oc & 31u)));
+        if (moved)
+            for (; eo < steps; ++eo) emit(eo, false, false, (T)0);
+        flush();
+        if (dbits) atomicAnd(dead + rw, ~dbits);
+        atomicAnd(dirty + (b >> 5), ~(1u << (b & 31u)));
+    }
+}
+
 // ---- decode
 // per metadata word: run starts, occupied bits, slots in use (counts[0 / 1 / 2][w]); marks[0] = the first slot with continuation = shifted = 0
 // (the anchor x above), marks[1] = the first empty slot (0xFFFFFFFF: none, the table is full)
@@ -258,6 +380,37 @@ extern "C" int psk_qf_check_alt(uint32_t q, const void *filter_dev, const uint32
     const psk::QfTable t{filter_dev, occupied_dev, continuation_dev, shifted_dev, q};
     hipLaunchKernelGGL(k_qf_check_alt, dim3(grid_for_keys(n)), dim3(kBlock), 0, (hipStream_t)stream, t, hashes_dev, n, out_dev);
     HIP_TRY(hipGetLastError());
+    return PSK_OK;
+}
+
+// the table without the hashes of the batch: `for h in hashes: remove_alt(h)` (quotientfilter.py:177-185, :396-469) on a table with an empty slot.
+// scratch_dev (uint32): dead[words], dirty[words], the list cursor and a pad word -- zero on entry, zero again when the call has run -- then n list entries.
+extern "C" int psk_qf_remove_alt(uint32_t q, void *filter_dev, uint32_t *occupied_dev, uint32_t *continuation_dev, uint32_t *shifted_dev,
+                                 const uint32_t *sorted_hashes_dev, uint64_t n, uint32_t *scratch_dev, uint32_t *removed_dev, int device, void *stream)
+{
+    PSK_TRY(check_q(q));
+    if (q < 5) return fail(PSK_EINVAL, "a table of 2^%u slots shares one metadata word between all its slots: rebuild it (psk_qf_build)", q);
+    if (!filter_dev || !occupied_dev || !continuation_dev || !shifted_dev || !removed_dev) return fail(PSK_EINVAL, "NULL table pointer");
+    if (n > (1ull << 32)) return fail(PSK_EINVAL, "%llu hashes cannot be distinct", (unsigned long long)n);
+    if (n && (!sorted_hashes_dev || !scratch_dev)) return fail(PSK_EINVAL, "NULL argument");
+    PSK_USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(removed_dev, 0, 4, st));
+    if (!n) return PSK_OK;
+    const uint32_t nwords = words_of(q);
+    uint32_t *dead = scratch_dev, *dirty = scratch_dev + nwords, *cursor = scratch_dev + 2ull * nwords, *list = cursor + 2;
+    const psk::QfTable t{filter_dev, occupied_dev, continuation_dev, shifted_dev, q};
+    hipLaunchKernelGGL(k_qf_locate, dim3(grid_for_keys(n)), dim3(kBlock), 0, st, t, sorted_hashes_dev, n, dead, dirty, cursor, list, removed_dev);
+    const unsigned grid = grid_of(n);
+    const uint32_t rbits = 32 - q;
+    if (rbits <= 8)
+        hipLaunchKernelGGL((k_qf_repack<uint8_t>), dim3(grid), dim3(kBlock), 0, st, (uint8_t *)filter_dev, occupied_dev, continuation_dev, shifted_dev, q, dead, dirty, cursor, list, n);
+    else if (rbits <= 16)
+        hipLaunchKernelGGL((k_qf_repack<uint16_t>), dim3(grid), dim3(kBlock), 0, st, (uint16_t *)filter_dev, occupied_dev, continuation_dev, shifted_dev, q, dead, dirty, cursor, list, n);
+    else
+        hipLaunchKernelGGL((k_qf_repack<uint32_t>), dim3(grid), dim3(kBlock), 0, st, (uint32_t *)filter_dev, occupied_dev, continuation_dev, shifted_dev, q, dead, dirty, cursor, list, n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(cursor, 0, 4, st));
     return PSK_OK;
 }
 

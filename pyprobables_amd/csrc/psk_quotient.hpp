@@ -91,7 +91,10 @@ __device__ __forceinline__ uint32_t qf_rem(const void *f, uint32_t rbits, uint32
 // A table of 8 or 16 slots is one word whose pattern is replicated to 32 bits: the ring of 32 virtual slots is the table unrolled, every
 // walk (shorter than the table) stays exact, and a slot's remainder is at (virtual position mod size).  Every loop is bounded by the
 // table's size, so a table that is not a quotient filter's (a caller's garbage) ends in `false`, never in a spin.
-__device__ inline bool qf_contains(const QfTable &t, uint32_t h)
+//
+// qf_find is that walk with two by-products for removal (psk_quotient.hip k_qf_locate): the slot the hash sits in and the start of its cluster, the slot
+// where the walk back stopped.  qf_contains drops both, and the compiler with them.
+__device__ inline bool qf_find(const QfTable &t, uint32_t h, uint32_t &slot, uint32_t &start)
 {
     const uint32_t rbits = 32u - t.q, smask = (1u << t.q) - 1u;
     const uint32_t quot = h >> rbits, rem = h & ((1u << rbits) - 1u);
@@ -117,6 +120,7 @@ __device__ inline bool qf_contains(const QfTable &t, uint32_t h)
         upto = before = 0xFFFFFFFFu;
     }
     if (!found) return false;
+    start = ((w << 5) | j) & smask;
 
     uint32_t from = 0xFFFFFFFFu << j, c = 0;
     found = false;
@@ -137,7 +141,8 @@ __device__ inline bool qf_contains(const QfTable &t, uint32_t h)
     if (!found) return false;
 
     for (uint32_t steps = 0; steps <= smask; ++steps) {
-        const uint32_t v = qf_rem(t.filter, rbits, ((w << 5) | j) & smask);
+        slot = ((w << 5) | j) & smask;
+        const uint32_t v = qf_rem(t.filter, rbits, slot);
         if (v >= rem) return v == rem;  // the run is sorted: the reference stops at the first remainder > r too
         if (++j == 32u) {
             j = 0;
@@ -147,6 +152,12 @@ __device__ inline bool qf_contains(const QfTable &t, uint32_t h)
         if (!((c >> j) & 1u)) return false;  // the run ended
     }
     return false;
+}
+
+__device__ __forceinline__ bool qf_contains(const QfTable &t, uint32_t h)
+{
+    uint32_t slot = 0, start = 0;
+    return qf_find(t, h, slot, start);
 }
 
 template <class Src>

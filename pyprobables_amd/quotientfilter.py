@@ -7,10 +7,17 @@ deduplicate the hashes (torch: rocPRIM's radix sort), place them with one prefix
 reference's bit for bit (DESIGN.md "Quotient filter"; tests/test_quotient_model.py ties the layout rule to the live reference).
 Adding to a non-empty filter is decode + concatenate + sort/unique + rebuild, exact for the same reason.
 
+Removal is a batch call, ``remove_many`` / ``remove_alt_many``: the reference's ``remove_alt`` leaves the canonical table of the remaining set
+whenever the table has an empty slot (tests/test_quotient_remove_model.py), so a batch is exact however it is carried out -- by repairing the
+hit clusters in place (``psk_qf_remove_alt``, DESIGN.md "Quotient filter: removal") or by decode + set difference + rebuild.  The reference
+never decrements ``_elements_added`` in a removal and resets it only in a resize; ``elements_added``, ``load_factor``, the auto-expand test and
+the "insufficient space" test follow that counter (held + removals since the last resize), ``elements_held`` is the true count.
+
 Deviations from the reference, all deliberate:
 
-* ``remove`` / ``remove_alt`` raise :class:`NotSupportedError`: the reference's removal raises ``IndexError: pop from empty list`` in
-  ``_fixup_cluster`` on ordinary inputs (q = 3, load 0.3, quotients near the end of the table); a crash is not reproduced.
+* the per-key ``remove`` / ``remove_alt`` still raise :class:`NotSupportedError`; removal is available as ``remove_many`` / ``remove_alt_many``.
+* ``remove_many`` / ``remove_alt_many`` on a completely full table give the canonical table of the remaining set (the reference's removal can
+  spin forever there or leave a table that is not canonical).
 * ``auto_expand=False`` and more distinct hashes than slots: :class:`QuotientFilterError` with the reference's message, raised BEFORE
   the table changes (the reference raises mid-stream and keeps the part it had inserted).
 * ``get_hashes()`` of a completely full table returns the hashes in ascending order (the reference's walk to the first empty slot
@@ -38,6 +45,12 @@ except Exception:  # pragma: no cover
     torch = None
 
 _I32_MIN = -(2**31)
+# ``_remove_policy = "auto"``: a batch of up to this fraction of the hashes held is repaired in place, a larger one rebuilds the table.
+# profiles/quotient_remove_bench.txt (scripts/bench_quotient_remove.py; load 0.8, end to end, m distinct present hashes of `held`):
+#   q = 24 (13.4 M held)  in place 0.29 ms at m = 2^10, 0.38 ms at 2^16, 2.0 ms at 2^22 (0.31 of held); the rebuild 3.2 - 3.4 ms at every m
+#   q = 20 (839 K held)   in place 0.27 ms at 2^10, 0.44 ms at 2^18 (0.31 of held), 0.59 ms at 2^19 (0.62); the rebuild 0.48 - 0.58 ms
+# In place wins up to 0.31 of held at both sizes (by 1.7 x and 1.2 x there) and ties at 0.62 at q = 20; the constant lies between the two.
+REMOVE_LOCAL_MAX_FRACTION = 0.5
 
 
 def _check_quotient(quotient: int) -> None:
@@ -71,28 +84,48 @@ def _after_resize(quotient: int, held: int, max_load_factor: float) -> int:
     return quotient
 
 
-def expanded_quotient(quotient: int, held: int, counts_after, max_load_factor: float = 0.85) -> int:
+def expanded_quotient(quotient: int, held: int, counts_after, max_load_factor: float = 0.85, stale: int = 0) -> int:
     """The quotient an auto-expanding filter ends with.  ``held`` distinct hashes are in the table, ``counts_after[i]`` (ascending; a
     torch tensor or anything ``torch.as_tensor`` takes) is the distinct count after call i of the stream.
 
     The reference tests ``load_factor >= max_load_factor`` at the START of every ``add_alt`` call, duplicates included
     (quotientfilter.py:161), so the table doubles only if another call FOLLOWS the one that reached the threshold: the crossing index
-    is the first i with ``counts_after[i] >= threshold``; a resize happens iff it is not the last call.  Repeats at the new size."""
+    is the first i with ``counts_after[i] >= threshold``; a resize happens iff it is not the last call.  Repeats at the new size.
+
+    ``stale``: successful removals since the last resize.  The reference's counter is the true count plus these until the first doubling
+    of the stream resets it (``resize`` re-adds what the table holds into fresh parameters); behind that the stream is judged on true counts."""
     cum = torch.as_tensor(counts_after, dtype=torch.int64)
     m = int(cum.numel())
     nxt = 0  # the first call whose load test has not run yet
     while nxt < m:
         t = resize_threshold(quotient, max_load_factor)
-        if held >= t:
+        if held + stale >= t:
             call = nxt
-        else:  # calls behind the first j with cum[j] >= t start with the threshold reached
-            call = max(nxt, int(torch.searchsorted(cum, torch.tensor([t], dtype=torch.int64, device=cum.device))[0]) + 1)
+        else:  # calls behind the first j with cum[j] + stale >= t start with the threshold reached
+            call = max(nxt, int(torch.searchsorted(cum, torch.tensor([t - stale], dtype=torch.int64, device=cum.device))[0]) + 1)
         if call >= m:
             break
         quotient = _after_resize(quotient, held if call == 0 else int(cum[call - 1]), max_load_factor)
         _check_quotient(quotient)
+        stale = 0
         nxt = call + 1  # that call inserts into the larger table without another test
     return quotient
+
+
+def plan_add(quotient: int, held: int, stale: int, counts_after, auto_expand: bool, max_load_factor: float = 0.85) -> tuple[int, int]:
+    """The host side of one ``add_alt`` stream: -> (quotient, stale) behind it.  ``held`` distinct hashes are in the table, ``stale`` removals
+    have succeeded since the last resize, ``counts_after[i]`` is the true distinct count after call i (non-empty).  Raises the reference's
+    "insufficient space" (quotientfilter.py:357-358: ``_add`` compares ITS counter with the size, so slots may be free) before anything changes."""
+    cum = torch.as_tensor(counts_after, dtype=torch.int64)
+    total = int(cum[-1])
+    q = quotient
+    if auto_expand and total + stale >= resize_threshold(q, max_load_factor):
+        q = expanded_quotient(q, held, cum, max_load_factor, stale)  # the threshold is reached inside this stream: whether (and how often) the table doubles depends on WHERE
+    if q != quotient:
+        stale = 0
+    if total + stale > (1 << q):
+        raise QuotientFilterError("Unable to insert the element due to insufficient space")
+    return q, stale
 
 
 def _is_default_hash(hash_function) -> bool:
@@ -131,8 +164,9 @@ class QuotientFilter:
     def _set_params(self, quotient: int) -> None:
         self._q, self._r, self._size = quotient, 32 - quotient, 1 << quotient
         self._bits_per_elm = bits_per_element(quotient)
-        self._elements_added = 0
+        self._held = self._stale = 0  # slots in use; successful removals since these parameters were set (the reference's counter is their sum)
         self._filter = self._occ = self._cont = self._sh = None  # allocated by the first call that touches the table (_alloc)
+        self._remove_scratch = None
 
     def _alloc(self) -> None:
         """the four arrays, zeroed, in HBM.  No device, no table: every call that needs one raises (there is no CPU fallback); the
@@ -171,8 +205,13 @@ class QuotientFilter:
 
     @property
     def elements_added(self) -> int:
-        """int: The number of (distinct) elements added to the filter"""
-        return self._elements_added
+        """int: The reference's counter: the (distinct) elements added since the last resize, removed ones included"""
+        return self._held + self._stale
+
+    @property
+    def elements_held(self) -> int:
+        """int: The number of (distinct) elements in the filter"""
+        return self._held
 
     @property
     def bits_per_elm(self) -> int:
@@ -182,7 +221,7 @@ class QuotientFilter:
     @property
     def load_factor(self) -> float:
         """float: The load factor of the filter"""
-        return self._elements_added / self._size
+        return self.elements_added / self._size
 
     @property
     def auto_expand(self) -> bool:
@@ -311,7 +350,7 @@ class QuotientFilter:
         scratch = torch.empty(n // 1024 + 2, dtype=torch.int32, device=self._dev())
         N.check(N.lib().psk_qf_build(self._q, sorted_bits.data_ptr() if n else None, n, self._filter.data_ptr(), self._occ.data_ptr(),
                                      self._cont.data_ptr(), self._sh.data_ptr(), scratch.data_ptr(), self._device, self._stream))
-        self._elements_added = n
+        self._held = n
 
     def _table_args(self):
         self._alloc()
@@ -319,7 +358,7 @@ class QuotientFilter:
 
     def _decode(self):
         """-> (hashes of the table ascending, int32 bit patterns on the device; first empty slot or None)"""
-        n = self._elements_added
+        n = self._held
         if n == 0:
             return torch.empty(0, dtype=torch.int32, device=self._dev()), 0
         words = int(self._occ.numel())
@@ -349,12 +388,12 @@ class QuotientFilter:
         m = int(bits.numel())
         if m == 0:
             return
-        held = self._elements_added
+        held, stale = self._held, self._stale
         old = self._decode()[0] if held else None
         union = self._usort(bits if old is None else torch.cat([old, bits]), unique=True)
         total = int(union.numel())
         q = self._q
-        if self._auto_resize and total >= resize_threshold(q, self._max_load_factor):
+        if self._auto_resize and total + stale >= resize_threshold(q, self._max_load_factor):
             # the threshold is reached inside this stream: whether (and how often) the table doubles depends on WHERE
             key = bits ^ _I32_MIN
             order = torch.sort(key, stable=True)
@@ -364,12 +403,13 @@ class QuotientFilter:
                 first &= ~torch.isin(order.values, old ^ _I32_MIN)
             new = torch.zeros(m, dtype=torch.int64, device=bits.device)
             new[order.indices] = first.to(torch.int64)
-            q = expanded_quotient(q, held, held + torch.cumsum(new, 0), self._max_load_factor)
-        if total > (1 << q):  # (quotientfilter.py:357-358, raised there by the insert that finds the table full)
-            raise QuotientFilterError("Unable to insert the element due to insufficient space")
+            q, stale = plan_add(q, held, stale, held + torch.cumsum(new, 0), True, self._max_load_factor)
+        else:
+            q, stale = plan_add(q, held, stale, [total], False)  # (quotientfilter.py:357-358, raised there by the insert that finds its counter at the size)
         if q != self._q:
             self._set_params(q)
         self._build(union)
+        self._stale = stale
 
     def add(self, key: KeyT) -> None:
         """Add key to the quotient filter (quotientfilter.py:144-152)"""
@@ -394,6 +434,57 @@ class QuotientFilter:
 
     def remove_alt(self, _hash: int) -> None:
         self.remove(b"")
+
+    # ------------------------------------------------------------------ batch removal
+    _remove_policy = "auto"  # "local": repair the hit clusters in place; "rebuild": decode, drop, build; "auto": by batch size (tests force each)
+
+    def _remove_bits(self, bits) -> int:
+        """the stream `bits` (int32 bit patterns) through ``remove_alt`` one after the other -> how many hashes left the table"""
+        if self._remove_policy not in ("auto", "local", "rebuild"):
+            raise ValueError(f"unknown _remove_policy {self._remove_policy!r}")
+        held = self._held
+        if int(bits.numel()) == 0 or held == 0:
+            return 0
+        gone = self._usort(bits, unique=True)
+        local = self._remove_policy == "local" or (self._remove_policy == "auto" and int(gone.numel()) <= held * REMOVE_LOCAL_MAX_FRACTION)
+        # a full table: the reference may not return, the canonical table of the rest is the defined answer and the rebuild gives it;
+        # q < 5: the table's metadata is one replicated word, which the in-place kernels do not take
+        if held == self._size or self._q < 5:
+            local = False
+        removed = self._remove_local(gone) if local else self._remove_rebuild(gone)
+        self._held = held - removed
+        self._stale += removed  # (the reference's `_elements_added` does not go down: quotientfilter.py:396-414 never touches it)
+        return removed
+
+    def _remove_local(self, gone) -> int:
+        n = int(gone.numel())
+        words = int(self._occ.numel())
+        if self._remove_scratch is None or int(self._remove_scratch.numel()) < 2 * words + 2 + n:
+            self._remove_scratch = torch.zeros(2 * words + 2 + max(n, 1024), dtype=torch.int32, device=self._dev())  # the kernels hand it back zeroed
+        count = torch.empty(1, dtype=torch.int32, device=self._dev())
+        scratch, self._remove_scratch = self._remove_scratch, None  # (a call that fails may leave bits behind: only a call that ran gives it back)
+        N.check(N.lib().psk_qf_remove_alt(*self._table_args(), gone.data_ptr(), n, scratch.data_ptr(), count.data_ptr(), self._device, self._stream))
+        removed = int(count.item())
+        self._remove_scratch = scratch
+        return removed
+
+    def _remove_rebuild(self, gone) -> int:
+        old = self._decode()[0]
+        at = torch.searchsorted(gone ^ _I32_MIN, old ^ _I32_MIN).clamp_(max=int(gone.numel()) - 1)
+        keep = old[gone[at] != old]
+        removed = int(old.numel() - keep.numel())
+        if removed:
+            self._build(keep)
+        return removed
+
+    def remove_many(self, keys) -> int:
+        """``for key in keys: remove(key)`` of the reference as one batch; keys as for ``add_many``.  Absent keys are no-ops.
+        Returns the number of hashes removed."""
+        return self._remove_bits(self._hash_keys(keys))
+
+    def remove_alt_many(self, hashes) -> int:
+        """``for h in hashes: remove_alt(h)`` of the reference as one batch; hashes as for ``add_alt_many``.  Returns the number removed."""
+        return self._remove_bits(self._as_bits(hashes))
 
     # ------------------------------------------------------------------ lookup
     def check_many(self, keys):
