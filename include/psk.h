@@ -127,7 +127,9 @@ int psk_device_count(int *count);
  * polls its completion mailbox before it waits for the stream; 0 = never poll); read-only counters "cbf_ordered_replays",
  * "update_window_folds", "update_window_replays", "cms_small_weights_used", "cbf_lookup_shadow_hits", "cms_running_fast",
  * "cms_running_sequential" (psk_cms_add_running calls that took the parallel passes / the one-lane kernel), "cms_update_running_fast",
- * "cms_update_running_sequential" (the same for psk_cms_update_running).
+ * "cms_update_running_sequential" (the same for psk_cms_update_running), "cbf_running_fast_chunks", "cbf_running_replayed_chunks",
+ * "cbf_running_sequential" (psk_cbf_add_running / psk_cbf_update_running: chunks served by the parallel passes, chunks replayed in order,
+ * calls that were not eligible).
  * The bench build (-DPSK_BENCH_KNOBS=1, libpsk_hip_knobs.so) has one more option, "part_debug": the ablation / phase-profile bits of the
  * measuring tools; this library answers "unknown option" to it.  The A/B switches of experiments that were measured and dropped are gone
  * with their code (NOTES.md). */
@@ -263,6 +265,25 @@ int psk_flush(psk_sketch *s, void *stream);
 int psk_cbf_update_ordered(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n,
                            uint32_t key_len, const int64_t *weights, int opmode, int where, uint32_t *out,
                            void *stream);
+/* countingbloom.py:135-208 for a whole ORDERED batch in parallel: out[i] (uint32[n]), the table and the PSK_CTR_ADDED / _REMOVED / _SATURATED /
+ * _ABS_BOUND tallies end exactly as psk_cbf_update_ordered(..., PSK_OP_SIGNED, ...) leaves them for the same stream.  An op acts on each of
+ * its counters as a map (a, p): x -> (x == MAX || x + p >= MAX) ? MAX : x + a, MAX = 2^32 - 1 sticky; an add is (w, w), a remove that finds
+ * its key with at least w is (-w, -inf), and (a1, p1) then (a2, p2) is (a1 + a2, max(p1, a1 + p2)).  A counter's value in front of an op is
+ * a segmented scan of these maps in arrival order per counter: a hash pass (probe e = i * k + s), a stable radix sort of (counter, e), the
+ * scan, a per-op pass -- over ordered chunks of at most min(2^20, 2^23 / k) ops; the scratch does not grow with n.  The scan is optimistic
+ * (a remove takes min(min_val, w), nothing from an absent key): the per-op pass verifies every remove and every op that hits one counter
+ * twice, and the commit of a chunk waits for that verdict (one word read back per chunk).  A chunk that fails it has changed nothing and is
+ * replayed in order on one lane.  Tables with k > 64 or m > 2^32 walk the whole batch on one lane.  Read-only options
+ * "cbf_running_fast_chunks" / "cbf_running_replayed_chunks" count the chunks either way, "cbf_running_sequential" the calls that were not
+ * eligible.  Updates that wait in the engine (write-combined lists, the update window) reach the table first.  PSK_HOST / PSK_DEVICE as for
+ * psk_cms_add_running (PSK_DEVICE: out is a device pointer; the call still waits for each chunk's verdict); n == 0 runs nothing.
+ * psk_cbf_add_running: weights int32[n] >= 0 or NULL (= 1).  A negative weight in a PSK_HOST batch is PSK_EINVAL before anything changes;
+ * in a PSK_DEVICE batch it counts as 0 and is tallied in PSK_CTR_VIOLATIONS. */
+int psk_cbf_add_running(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n,
+                        uint32_t key_len, const int32_t *weights /* NULL = 1, >= 0 */, int where, uint32_t *out, void *stream);
+/* weights int32[n] or NULL (= +1): w >= 0 adds w, w < 0 removes -w; every int32 is valid (INT32_MIN removes 2^31) */
+int psk_cbf_update_running(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n,
+                           uint32_t key_len, const int32_t *weights /* NULL = +1 */, int where, uint32_t *out, void *stream);
 
 /* ---------------------------------------------------------- CountMinSketch
  * bins row-major by depth: bin = (h_i % width) + i*width, i < depth (countminsketch.py:275)

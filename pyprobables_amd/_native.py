@@ -70,6 +70,8 @@ PROTOTYPES = {
     "psk_cms_check": (_int, [_vp, *_KEYS, _int, _int, _vp, _vp]),
     "psk_cms_check_meanmin": (_int, [_vp, *_KEYS, _int, _i64, _vp, _vp]),
     "psk_cms_update_ordered": (_int, [_vp, *_KEYS, _vp, _int, _int, _i64, _int, _vp, _vp]),
+    "psk_cbf_add_running": (_int, [_vp, *_KEYS, _vp, _int, _vp, _vp]),
+    "psk_cbf_update_running": (_int, [_vp, *_KEYS, _vp, _int, _vp, _vp]),
     "psk_cms_add_running": (_int, [_vp, *_KEYS, _vp, _int, _int, _i64, _vp, _vp, _vp]),
     "psk_cms_update_running": (_int, [_vp, *_KEYS, _vp, _int, _int, _i64, _vp, _vp, _vp]),
     "psk_fnv1a_hash": (_int, [*_KEYS, _u32, _int, _vp, _int, _vp]),

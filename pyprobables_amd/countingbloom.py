@@ -2,9 +2,12 @@
 
 Drop-in for the hot path of ``probables.CountingBloomFilter`` (``probables/blooms/countingbloom.py``).
 
-Two execution modes
+Three execution modes
   * single-key ``add`` / ``remove`` (and ``update_ordered``): the reference semantics executed literally,
     in order, on the GPU -- exact for any stream, including the per-op return value;
+  * ``add_many_ordered`` / ``update_many_ordered`` / ``remove_many_ordered``: the same ordered semantics for a
+    whole batch, every op's return value included, as parallel passes (a scan per counter, verified, replayed in
+    order where the verification fails) -- exact for any stream;
   * ``add_many`` / ``remove_many``: unordered batches with k atomics per key.  Bit-exact with the
     reference for well-formed streams (no counter saturates; every remove targets a key with at least
     ``num_els`` live inserts), which makes the result independent of the order inside the batch.
@@ -25,6 +28,7 @@ from .hashes import HashResultsT, KeyT
 from .keys import KeyBatch, pack_hashes
 
 _U32_MAX = 2**32 - 1
+_I32_MIN, _I32_MAX = -(2**31), 2**31 - 1
 _U64_MAX = 2**64 - 1
 
 
@@ -189,6 +193,90 @@ class CountingBloomFilter(BloomFilter):
         """execute a mixed stream strictly in order on the device: ``w >= 0`` adds ``w``, ``w < 0`` removes
         ``-w``; returns every op's reference return value (uint32[n])"""
         return self._ordered(self._batch(keys), signed_num_els, N.OP_SIGNED)
+
+    # -------------------------------------------------------------- ordered batches, in parallel (psk_cbf_add_running / _update_running)
+    @staticmethod
+    def _weight_range(w):
+        """(min, max) of a weight argument as Python integers, None for an empty one (a device tensor costs one small reduction and a
+        synchronisation here)"""
+        if hasattr(w, "is_cuda"):
+            return (int(w.min().item()), int(w.max().item())) if w.numel() else None
+        a = np.asarray(w)
+        return (int(a.min()), int(a.max())) if a.size else None
+
+    def _running(self, fn, b: KeyBatch, w, lo: int):
+        """every op's return value of the ordered batch, on the batch's side"""
+        keep: list = []
+        w_addr, _ = weights_arg(w, b.n, np.int32, b.where, keep, lo, _I32_MAX, self._tab.device)
+        addr, fin = self._tab.out_buffer(b, b.n, np.uint32, _torch_dtype("int32"))
+        N.check(fn(self._tab.handle, *b.args(), w_addr, b.where, addr or None, self._tab.stream))
+        self._release_borrowed()  # (the engine applied what was waiting before it touched the table)
+        self._dirty = True
+        return fin()
+
+    def _add_running(self, b: KeyBatch, num_els):
+        if num_els is not None:
+            r = self._weight_range(num_els)
+            if r and (r[0] < 0 or r[1] > _I32_MAX):
+                raise ValueError("add_many_ordered: num_els must lie in [0, 2**31 - 1] (update_ordered takes int64 weights and walks the "
+                                 "batch on its sequential kernel)")
+        return self._running(N.lib().psk_cbf_add_running, b, num_els, 0)
+
+    def _update_running(self, b: KeyBatch, signed_num_els):
+        w = signed_num_els
+        if w is None:
+            raise ValueError("update_many_ordered: signed_num_els is required (add_many_ordered / remove_many_ordered take None)")
+        if not (hasattr(w, "is_cuda") and w.dtype.is_signed and w.element_size() <= 4):  # (an int32 tensor cannot be outside)
+            r = self._weight_range(w)
+            if r and (r[0] < _I32_MIN or r[1] > _I32_MAX):
+                raise ValueError("update_many_ordered: weights must lie in [-2**31, 2**31 - 1]; update_ordered takes int64 weights "
+                                 "(and walks the batch on its sequential kernel)")
+        return self._running(N.lib().psk_cbf_update_running, b, w, _I32_MIN)
+
+    @classmethod
+    def _negated(cls, num_els):
+        """the weights of ``remove_many_ordered`` as ``update_many_ordered`` takes them"""
+        if num_els is None:
+            return -1
+        r = cls._weight_range(num_els)
+        if r and (r[0] < 0 or r[1] > _I32_MAX):
+            raise ValueError("remove_many_ordered: num_els must lie in [0, 2**31 - 1] (update_many_ordered removes 2**31 with the weight -2**31)")
+        if hasattr(num_els, "is_cuda"):
+            return -num_els
+        return -np.asarray(num_els, dtype=np.int64) if np.ndim(num_els) else -int(num_els)
+
+    def add_many_ordered(self, keys, num_els=None):
+        """the batch form of ``add`` (countingbloom.py:125-155): the counters and ``elements_added`` end as the loop
+        ``for key, w in zip(keys, num_els): add(key, w)`` leaves them and entry i of the result is what that loop's i-th ``add`` returns
+        -- uint32 numpy for host batches, an int32-bits torch tensor for device batches, as ``check_many``.  ``keys`` / ``num_els`` as
+        for ``add_many``; ``num_els`` must lie in [0, 2**31 - 1] (ValueError before anything changes).  Where the reference would raise
+        OverflowError (a counter beyond 2^32 - 1) the counter stays at 2^32 - 1, as in ``add``."""
+        return self._add_running(self._batch(keys), num_els)
+
+    def add_alt_many_ordered(self, hashes, num_els=None):
+        """``add_many_ordered`` for pre-computed hashes (a (n, number_hashes) uint64 array / tensor)"""
+        return self._add_running(pack_hashes(hashes, self._number_hashes), num_els)
+
+    def update_many_ordered(self, keys, signed_num_els):
+        """the batch form of a mixed stream of ``add`` and ``remove`` (countingbloom.py:125-208): ``w >= 0`` adds ``w``, ``w < 0``
+        removes ``-w`` (``-2**31`` removes 2^31); results as ``add_many_ordered``.  Exact for ANY stream -- removes of absent keys,
+        partial removes, counters on 2^32 - 1 --: the engine scans the batch in parallel, verifies every remove, and replays a chunk in
+        order where the verification fails.  Weights outside int32 raise ValueError before anything changes; ``update_ordered`` keeps
+        its int64 weights and its sequential kernel."""
+        return self._update_running(self._batch(keys), signed_num_els)
+
+    def update_alt_many_ordered(self, hashes, signed_num_els):
+        """``update_many_ordered`` for pre-computed hashes"""
+        return self._update_running(pack_hashes(hashes, self._number_hashes), signed_num_els)
+
+    def remove_many_ordered(self, keys, num_els=None):
+        """the batch form of ``remove`` (countingbloom.py:176-208): ``update_many_ordered`` with the weights negated; ``num_els`` must
+        lie in [0, 2**31 - 1]"""
+        return self._update_running(self._batch(keys), self._negated(num_els))
+
+    def remove_alt_many_ordered(self, hashes, num_els=None):
+        """``remove_many_ordered`` for pre-computed hashes"""
+        return self._update_running(pack_hashes(hashes, self._number_hashes), self._negated(num_els))
 
     def check(self, key: KeyT) -> int:  # type: ignore[override]
         """countingbloom.py:157-164"""

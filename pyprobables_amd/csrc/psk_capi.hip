@@ -180,6 +180,9 @@ int64_t g_running_fast = 0;                // psk_cms_add_running calls that too
 int64_t g_running_sequential = 0;          // ... and the one-lane kernel
 int64_t g_update_running_fast = 0;         // psk_cms_update_running calls that took the parallel passes
 int64_t g_update_running_sequential = 0;   // ... and the one-lane kernel
+int64_t g_cbf_running_fast_chunks = 0;     // chunks of psk_cbf_add_running / _update_running the parallel passes served
+int64_t g_cbf_running_replayed_chunks = 0; // ... and those whose verification failed: replayed in order on one lane
+int64_t g_cbf_running_sequential = 0;      // calls of the two that were not eligible: the one-lane kernel for the whole batch
 // Process DEFAULTS of the per-sketch options, in HandleOpt order.  Nothing but the option calls and resolve_options touches them: the engine
 // reads psk_sketch::eff.
 static int64_t g_sketch_default[HO_COUNT] = {
@@ -257,6 +260,9 @@ const OptDesc kOptions[] = {
     {"cms_running_sequential", &g_running_sequential, kOptReadOnly, kAny},
     {"cms_update_running_fast", &g_update_running_fast, kOptReadOnly, kAny},
     {"cms_update_running_sequential", &g_update_running_sequential, kOptReadOnly, kAny},
+    {"cbf_running_fast_chunks", &g_cbf_running_fast_chunks, kOptReadOnly, kAny},
+    {"cbf_running_replayed_chunks", &g_cbf_running_replayed_chunks, kOptReadOnly, kAny},
+    {"cbf_running_sequential", &g_cbf_running_sequential, kOptReadOnly, kAny},
     // measuring tools (bench builds only)
     {"part_debug", &g_part_debug, kOptKnob, kAny},
 };

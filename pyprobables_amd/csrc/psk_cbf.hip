@@ -3,6 +3,7 @@
 #include "psk_stage.hpp"
 #include "psk_nibble.hpp"
 #include "psk_window.hpp"
+#include "psk_cbf_running.hpp"
 
 // ----------------------------------------------------- CountingBloomFilter
 // the direct kernels of an unordered CBF update (w = nullptr: unit weights)
@@ -726,4 +727,93 @@ extern "C" int psk_cbf_update_ordered(psk_sketch *s, int layout, const void *dat
         }));
     }
     return finish(where, &o, st, &mb);
+}
+
+// countingbloom.py:135-208 for a whole ordered batch: the table, the handle's counters and EVERY op's return value as the one-lane loop
+// (k_cbf_ordered, PSK_OP_SIGNED) leaves them.  The optimistic parallel passes of psk_cbf_running.hpp chunk by chunk wherever they apply
+// (k <= kMaxKOrdered, m <= 2^32); a chunk whose verification raised its flag has changed nothing and is replayed in order on one lane
+// before the next chunk starts.  Anything else: the one-lane kernel for the whole call.  Read-only options "cbf_running_fast_chunks" /
+// "cbf_running_replayed_chunks" / "cbf_running_sequential" count the chunks either way and the calls that were not eligible.
+// ADDONLY: psk_cbf_add_running (weights >= 0 is the entry's contract).
+template <bool ADDONLY>
+static int cbf_running(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, const int32_t *weights, int where,
+                       uint32_t *out, void *stream)
+{
+    CHECK_HANDLE(s, PSK_KIND_CBF);
+    PSK_TRY(check_hashes_width(s, layout, key_len));
+    if (where != PSK_HOST && where != PSK_DEVICE) return fail(PSK_EINVAL, "`where` must be PSK_HOST or PSK_DEVICE");
+    if (n && !out) return fail(PSK_EINVAL, "out is NULL");
+    if (ADDONLY && where == PSK_HOST && weights)
+        for (uint64_t i = 0; i < n; ++i)
+            if (weights[i] < 0) return fail(PSK_EINVAL, "ordered add: weight %d of op %llu is negative", weights[i], (unsigned long long)i);
+    hipStream_t st = (hipStream_t)stream;
+    Batch b;
+    if (n == 0) return stage_batch(s->s_keys, s->s_offs, layout, data, offsets, n, key_len, where, st, &b);  // (validated; nothing runs)
+    PSK_TRY(flush_combined(s, st));  // write-combined and windowed updates reach the table before anything else touches it
+    PSK_TRY(stage_batch(s->s_keys, s->s_offs, layout, data, offsets, n, key_len, where, st, &b));
+    const int32_t *w;
+    PSK_TRY(stage_vec(s->s_w, weights, n, where, st, &w));
+    OutBuf o;
+    PSK_TRY(stage_out(s->s_out, out, n * 4, where, &o));
+    if (s->k >= 1 && s->k <= (uint32_t)kMaxKOrdered && s->m <= (1ULL << 32)) {
+        CbfRunArena a;
+        PSK_TRY(cbf_running_arena(s, n, &a));
+        for (uint64_t base = 0; base < n; base += a.l.cap) {
+            const uint32_t nc = (uint32_t)(n - base < a.l.cap ? n - base : a.l.cap);
+            PSK_TRY(with_source(b, [&](auto src) {
+                return with_pow2(s, [&](auto P) {
+                    hipLaunchKernelGGL((k_cbfr_hash<decltype(src), P.value>), dim3(grid_for_keys(nc)), dim3(kBlock), 0, st, src, s->md, s->k, base, nc, a.bins);
+                    HIP_TRY(hipGetLastError());
+                    return (int)PSK_OK;
+                });
+            }));
+            bool clean = false;
+            PSK_TRY(cbf_running_chunk(s, a, w, base, nc, ADDONLY, (uint32_t *)o.dev, st, &clean));
+            __atomic_add_fetch(clean ? &g_cbf_running_fast_chunks : &g_cbf_running_replayed_chunks, 1, __ATOMIC_RELAXED);
+            if (clean) continue;
+            PSK_TRY(with_source(b, [&](auto src) {
+                return with_pow2(s, [&](auto P) {
+                    hipLaunchKernelGGL((k_cbfr_replay<decltype(src), P.value, ADDONLY>), dim3(1), dim3(64), 0, st, src, (uint32_t *)s->table, s->md, s->k, w, base, nc,
+                                       (uint32_t *)o.dev, (unsigned long long *)s->ctr);
+                    HIP_TRY(hipGetLastError());
+                    return (int)PSK_OK;
+                });
+            }));
+        }
+    } else {  // one lane, one op after the other (int64 weights: widened in front of it)
+        __atomic_add_fetch(&g_cbf_running_sequential, 1, __ATOMIC_RELAXED);
+        uint64_t *wide = nullptr;
+        if (s->k > (uint32_t)kMaxKOrdered) {
+            PSK_TRY(ensure(s->s_aux, 16ULL * s->k));
+            wide = (uint64_t *)s->s_aux.p;
+        }
+        const int64_t *w64 = nullptr;
+        if (w) {
+            PSK_TRY(ensure(s->s_vals, 8 * n));
+            hipLaunchKernelGGL((k_cbfr_widen<ADDONLY>), dim3(grid_for_keys(n)), dim3(kBlock), 0, st, w, n, (int64_t *)s->s_vals.p, (unsigned long long *)s->ctr);
+            HIP_TRY(hipGetLastError());
+            w64 = (const int64_t *)s->s_vals.p;
+        }
+        PSK_TRY(with_source(b, [&](auto src) {
+            return with_pow2(s, [&](auto P) {
+                hipLaunchKernelGGL((k_cbf_ordered<decltype(src), P.value>), dim3(1), dim3(64), 0, st, src, (uint32_t *)s->table, s->md, s->k, w64,
+                                   (int)(ADDONLY ? PSK_OP_ADD : PSK_OP_SIGNED), n, (uint32_t *)o.dev, (unsigned long long *)s->ctr, wide, (uint32_t *)nullptr, 0u);
+                HIP_TRY(hipGetLastError());
+                return (int)PSK_OK;
+            });
+        }));
+    }
+    return finish(where, &o, st);
+}
+
+extern "C" int psk_cbf_add_running(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len,
+                                   const int32_t *weights, int where, uint32_t *out, void *stream)
+{
+    return cbf_running<true>(s, layout, data, offsets, n, key_len, weights, where, out, stream);
+}
+
+extern "C" int psk_cbf_update_running(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len,
+                                      const int32_t *weights, int where, uint32_t *out, void *stream)
+{
+    return cbf_running<false>(s, layout, data, offsets, n, key_len, weights, where, out, stream);
 }

@@ -973,6 +973,67 @@ __global__ __launch_bounds__(kBlock) void k_cbf_remove(Src src, uint32_t *tab, M
 // ONE op (the per-key API) with k <= 64: lane s takes probe s, so the k hash chains and the k table round trips overlap instead of
 // queueing up behind one lane; a key whose probes collide (two probes, one counter -- the sequential semantics matter) and every longer
 // batch walk the literal loop below.  `mbox`: see mailbox_post.
+// what a stretch of the ordered loop adds to the handle's counters
+struct CbfOrderedTally {
+    unsigned long long added = 0, removed = 0, sat = 0, abs_sum = 0;
+};
+
+// The literal loop: ops [lo, hi) of the batch, one after the other, on the calling lane.  weight_of(i): the signed 64-bit weight of op i;
+// idx / vals: k words each.  (k_cbf_ordered walks a whole batch with it, k_cbfr_replay of psk_cbf_running.hpp one chunk.)
+template <class Src, bool POW2, class WeightOf>
+__device__ __forceinline__ void cbf_ordered_loop(const Src &src, uint32_t *tab, const Mod &md, uint32_t k, WeightOf weight_of, int opmode, uint64_t lo, uint64_t hi,
+                                                 uint32_t *out, uint64_t *idx, uint64_t *vals, CbfOrderedTally &t)
+{
+    for (uint64_t i = lo; i < hi; ++i) {
+        const typename Src::Key key = src.load(i);
+        int64_t w = weight_of(i);
+        bool rem = opmode == 1;
+        if (opmode == 2 && w < 0) { rem = true; w = -w; }
+        t.abs_sum += (unsigned long long)(w < 0 ? -w : w);
+        for (uint32_t s = 0; s < k; ++s) {
+            uint64_t h[1];
+            src.template hash<1>(key, i, s, h);
+            idx[s] = reduce<POW2>(md, h[0]);
+        }
+        uint32_t ret;
+        if (!rem) {  // countingbloom.py:135-155
+            uint64_t mn = ~0ULL;
+            for (uint32_t s = 0; s < k; ++s) vals[s] = (uint64_t)tab[idx[s]] + (uint64_t)w;  // :146 pre-read
+            for (uint32_t s = 0; s < k; ++s) {
+                if (vals[s] > 0xFFFFFFFFULL) { tab[idx[s]] = 0xFFFFFFFFu; vals[s] = 0xFFFFFFFFULL; ++t.sat; }
+                else tab[idx[s]] += (uint32_t)w;                                            // :153
+                mn = vals[s] < mn ? vals[s] : mn;
+            }
+            t.added += (uint64_t)w;
+            ret = (uint32_t)mn;
+        } else {  // countingbloom.py:186-208
+            uint32_t mn = 0xFFFFFFFFu;
+            for (uint32_t s = 0; s < k; ++s) mn = tab[idx[s]] < mn ? tab[idx[s]] : mn;
+            if (mn == 0xFFFFFFFFu) ret = 0xFFFFFFFFu;
+            else if (mn == 0) ret = 0;
+            else {
+                const uint32_t tr = (uint64_t)mn > (uint64_t)w ? (uint32_t)w : mn;
+                for (uint32_t s = 0; s < k; ++s)
+                    if (tab[idx[s]] < 0xFFFFFFFFu) tab[idx[s]] -= tr;
+                t.removed += tr;
+                ret = mn - tr;
+            }
+        }
+        if (out) out[i] = ret;
+    }
+}
+
+// the tallies of the ordered loop -> the handle's counters (one lane)
+__device__ __forceinline__ void cbf_ordered_book(unsigned long long *ctr, uint32_t k, const CbfOrderedTally &t)
+{
+    ctr[0] += t.added;
+    ctr[1] += t.removed;
+    ctr[3] += t.sat;
+    // every op moved a counter by at most k*|w|: keep the wrap-free bound an upper bound
+    const unsigned long long nb = ctr[4] + t.abs_sum * (unsigned long long)k;
+    ctr[4] = (nb < ctr[4] || nb > (1ULL << 62)) ? (1ULL << 62) : nb;
+}
+
 template <class Src, bool POW2>
 __global__ void k_cbf_ordered(Src src, uint32_t *tab, Mod md, uint32_t k, const int64_t *weights, int opmode,
                               uint64_t n, uint32_t *out, unsigned long long *ctr, uint64_t *wide, uint32_t *mbox, uint32_t seq)
@@ -1038,49 +1099,13 @@ __global__ void k_cbf_ordered(Src src, uint32_t *tab, Mod md, uint32_t k, const 
     if (threadIdx.x != 0) return;  // (out[0] is lane 0's own store: the fence in front of the mailbox below covers it)
     uint64_t idx_r[kMaxKOrdered], vals_r[kMaxKOrdered];
     uint64_t *idx = wide ? wide : idx_r, *vals = wide ? wide + k : vals_r;
-    for (uint64_t i = 0; i < (one_done ? 0 : n); ++i) {
-        const typename Src::Key key = src.load(i);
-        int64_t w = weights ? weights[i] : 1;
-        bool rem = opmode == 1;
-        if (opmode == 2 && w < 0) { rem = true; w = -w; }
-        abs_sum += (unsigned long long)(w < 0 ? -w : w);
-        for (uint32_t s = 0; s < k; ++s) {
-            uint64_t h[1];
-            src.template hash<1>(key, i, s, h);
-            idx[s] = reduce<POW2>(md, h[0]);
-        }
-        uint32_t ret;
-        if (!rem) {  // countingbloom.py:135-155
-            uint64_t mn = ~0ULL;
-            for (uint32_t s = 0; s < k; ++s) vals[s] = (uint64_t)tab[idx[s]] + (uint64_t)w;  // :146 pre-read
-            for (uint32_t s = 0; s < k; ++s) {
-                if (vals[s] > 0xFFFFFFFFULL) { tab[idx[s]] = 0xFFFFFFFFu; vals[s] = 0xFFFFFFFFULL; ++sat; }
-                else tab[idx[s]] += (uint32_t)w;                                            // :153
-                mn = vals[s] < mn ? vals[s] : mn;
-            }
-            added += (uint64_t)w;
-            ret = (uint32_t)mn;
-        } else {  // countingbloom.py:186-208
-            uint32_t mn = 0xFFFFFFFFu;
-            for (uint32_t s = 0; s < k; ++s) mn = tab[idx[s]] < mn ? tab[idx[s]] : mn;
-            if (mn == 0xFFFFFFFFu) ret = 0xFFFFFFFFu;
-            else if (mn == 0) ret = 0;
-            else {
-                const uint32_t tr = (uint64_t)mn > (uint64_t)w ? (uint32_t)w : mn;
-                for (uint32_t s = 0; s < k; ++s)
-                    if (tab[idx[s]] < 0xFFFFFFFFu) tab[idx[s]] -= tr;
-                removed += tr;
-                ret = mn - tr;
-            }
-        }
-        if (out) out[i] = ret;
-    }
-    ctr[0] += added;
-    ctr[1] += removed;
-    ctr[3] += sat;
-    // every op moved a counter by at most k*|w|: keep the wrap-free bound an upper bound
-    const unsigned long long nb = ctr[4] + abs_sum * (unsigned long long)k;
-    ctr[4] = (nb < ctr[4] || nb > (1ULL << 62)) ? (1ULL << 62) : nb;
+    CbfOrderedTally t;
+    t.added = added;
+    t.removed = removed;
+    t.sat = sat;
+    t.abs_sum = abs_sum;
+    cbf_ordered_loop<Src, POW2>(src, tab, md, k, [&](uint64_t i) -> int64_t { return weights ? weights[i] : 1; }, opmode, 0, one_done ? 0 : n, out, idx, vals, t);
+    cbf_ordered_book(ctr, k, t);
     if (mbox) {
         __threadfence_system();
         mailbox_post(mbox, seq);

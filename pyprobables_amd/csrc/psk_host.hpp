@@ -265,7 +265,7 @@ extern PSK_HIDDEN int64_t g_part_mode, g_part_max_keys, g_part_cache_bytes, g_pa
     g_window_force_fail, g_merge_single_rank, g_lazy_clear, g_host_poll_us,
     // read-only counters (handles on different threads bump them: relaxed atomic adds)
     g_cbf_ordered_replays, g_window_folds, g_window_replays, g_small_weights_used, g_cbf_shadow_hits, g_running_fast, g_running_sequential,
-    g_update_running_fast, g_update_running_sequential;
+    g_update_running_fast, g_update_running_sequential, g_cbf_running_fast_chunks, g_cbf_running_replayed_chunks, g_cbf_running_sequential;
 
 // slices of a table of `cells` cells; max_shift = log2(cells one LDS slice may hold)
 // target_lg: aim at 2^target_lg .. 2^(target_lg+1)-1 slices.  8 (one slice per CU or more) for the Bloom tables; the counter
