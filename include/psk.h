@@ -533,7 +533,9 @@ int psk_idx_resolve_ordered(const void *table_dev, const uint32_t *idx_dev, cons
 /* the same resolution with the per-bit scratch replaced by a bounded hash map (round 4): slots_dev = uint32[2][2^lg_slots], all-ones on entry
  * and on exit, 2^lg_slots >= 2 * n * k.  The caller walks an ordered chunk in sub-chunks of n keys -- resolve, insert, next -- so the scratch
  * is a few MB whatever the filter's size (psk_idx_resolve_ordered needs 4 bytes per filter BIT).  count_dev[0] += keys to insert,
- * count_dev[1] != 0: the map overflowed (cannot happen with the sizing above).  Enqueue only: no host synchronisation. */
+ * count_dev[1] != 0: the map overflowed (cannot happen with the sizing above).  Enqueue only: no host synchronisation.
+ * Bit position 2^32 - 1 is the map's "empty" marker and must not appear in idx_dev: this entry serves filters of m <= 2^32 - 1 bits
+ * (psk_idx_resolve_ordered has no such limit below m = 2^32). */
 int psk_idx_resolve_ordered_hashed(const void *table_dev, const uint32_t *idx_dev, const uint8_t *present_dev, uint64_t n, uint32_t k,
                                    void *slots_dev, uint32_t lg_slots, uint8_t *flag_dev, uint64_t *count_dev, int device, void *stream);
 int psk_idx_insert(void *table_dev, const uint32_t *idx_dev, const uint8_t *flag_dev, uint64_t n, uint32_t k, int device,
