@@ -208,6 +208,18 @@ int psk_bloom_check_bits(psk_sketch *s, int layout, const void *data, const uint
 int psk_bloom_check_begin(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len,
                           void *stream);
 int psk_bloom_check_finish(psk_sketch *s, uint8_t *out_dev, void *stream);
+/* The ordered batch: exactly the loop  `for key in batch: seen = key in blm; blm.add(key)`  (bloom.py:234-272), every key's answer at ITS place
+ * in the stream -- a key that repeats inside the batch is "seen" from its second occurrence on.  seen_out[i] = 0 / 1; *new_out (nullable) =
+ * the number of keys with seen == 0, which is also what the loop `if key not in blm: blm.add(key)` adds (the two loops leave the same table
+ * and the same flags).  Any key layout, any m < 2^63, both moduli.  The batch is resolved in ordered chunks of chunk_keys keys (0 = the
+ * default, min(2^18, 2^20 / k)), two launches per chunk, through an open-addressing map in the handle's scratch (counted by
+ * psk_scratch_bytes, freed by psk_release_scratch); the answers do not depend on the chunk.  PSK_HOST: host pointers, the call returns
+ * with the results in place.  PSK_DEVICE: device pointers, enqueue only.  n == 0 launches nothing and writes *new_out = 0.  A map that
+ * overflows (impossible with its sizing) is an error, never a silent answer: PSK_EHIP from this call (PSK_HOST) or from the next call of
+ * this entry point on the handle (PSK_DEVICE). */
+int psk_bloom_add_running(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n,
+                          uint32_t key_len, int where, uint64_t chunk_keys /* 0 = default */,
+                          uint8_t *seen_out /* [n] */, uint64_t *new_out /* nullable: #keys with seen == 0 */, void *stream);
 
 /* ----------------------------------------------------- CountingBloomFilter
  * Batches (weights: uint32[n] or NULL = all 1).  Round 4: the result of every batch equals the reference's per-key loop over it for ANY

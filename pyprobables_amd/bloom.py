@@ -287,6 +287,31 @@ class BloomFilter:
         """membership of every key: numpy bool[n] (host input) or torch bool[n] on the device (device input)"""
         return self._check_batch(self._batch(keys))
 
+    def _add_batch_ordered(self, b: KeyBatch, count_seen: bool):
+        self._flush()
+        addr, fin = self._tab.out_buffer(b, b.n, np.uint8, _torch_dtype("uint8"))
+        new = None
+        new_addr = None
+        if not count_seen:  # the only mode that needs the count of new keys (read back for a device batch)
+            new_addr, new = self._tab.out_buffer(b, 1, np.uint64, _torch_dtype("int64"))
+        N.check(N.lib().psk_bloom_add_running(self._tab.handle, *b.args(), b.where, 0, addr, new_addr, self._tab.stream))
+        self._els_added += b.n if count_seen else int(new()[0])
+        res = fin()
+        return res.view(np.bool_) if isinstance(res, np.ndarray) else res.view(_torch_dtype("bool"))
+
+    def add_many_ordered(self, keys, count_seen: bool = True):
+        """the loop ``seen = key in blm; blm.add(key)`` over a whole batch, exact: entry ``i`` of the result is what ``key_i in blm``
+        answers in front of the loop's ``i``-th ``add`` -- a key that repeats inside the batch is seen from its second occurrence on
+        (``check_many`` + ``add_many`` answers against the table before the batch).  numpy bool[n] for host batches, torch.bool on the
+        device for device batches, as ``check_many``.  ``count_seen=True``: ``elements_added`` grows by n, as the reference's ``add``
+        counts every call; ``count_seen=False``: the loop ``if key not in blm: blm.add(key)`` -- the same table and flags,
+        ``elements_added`` grows by the number of ``False`` entries."""
+        return self._add_batch_ordered(self._batch(keys), count_seen)
+
+    def add_alt_many_ordered(self, hashes, count_seen: bool = True):
+        """:meth:`add_many_ordered` for a pre-hashed batch: (n, >=k) uint64"""
+        return self._add_batch_ordered(pack_hashes(hashes, self._number_hashes), count_seen)
+
     def check_many_begin(self, keys) -> None:
         """first half of a split lookup: hash + partition a device-resident batch WITHOUT reading the table (so it can
         run while a multi-GPU merge of the table is in flight, see ``parallel.merge_bloom_async``).  Finish with

@@ -136,7 +136,7 @@ extern "C" int psk_cms_create(uint64_t width, uint32_t depth, int device, void *
 template <class F>
 static int for_each_scratch(psk_sketch *s, F &&f)
 {
-    for (DevBuf *b : {&s->s_keys, &s->s_offs, &s->s_w, &s->s_out, &s->s_aux, &s->s_part, &s->s_cnt, &s->s_flag, &s->s_spill, &s->s_tflag, &s->s_part2, &s->s_cnt2, &s->s_merge, &s->s_vals, &s->s_perm, &s->s_run, &s->s_tally,
+    for (DevBuf *b : {&s->s_keys, &s->s_offs, &s->s_w, &s->s_out, &s->s_aux, &s->s_part, &s->s_cnt, &s->s_flag, &s->s_spill, &s->s_omap, &s->s_tflag, &s->s_part2, &s->s_cnt2, &s->s_merge, &s->s_vals, &s->s_perm, &s->s_run, &s->s_tally,
                       &s->s_brw, &s->shadow.img, &s->s_wstat, &s->s_phase})
         PSK_TRY(f(*b, false));
     for (DevBuf *b : {&s->comb.add.keys, &s->comb.add.w, &s->comb.rem.keys, &s->comb.rem.w, &s->scat.add.part, &s->scat.add.cnt, &s->win.keys, &s->s_snap}) PSK_TRY(f(*b, true));

@@ -111,6 +111,8 @@ struct psk_sketch {
     DevBuf s_part, s_cnt;                      // partitioned path: bucket buffer + per-bucket fill counts
     DevBuf s_flag;                             // split lookup: "a segment overflowed" flag
     DevBuf s_spill;                            // Bloom insert after a deferred clear: [0] count, then the bit indices of overflowing probes
+    DevBuf s_omap;                             // psk_bloom_add_running: the open-addressing map of one ordered chunk; its pinned page holds the error word
+    uint32_t omap_seq = 0, omap_prev_lg = 0;   // ... the number of the handle's last ordered chunk (never 0 once used) and the log2 of the slots it used
     DevBuf s_tflag;                            // tile-flag Bloom lookups: one uint32 per pass-1 tile of a round; "flagged" = holds the round's
     uint32_t tflag_gen = 0;                    // generation number (never 0), so the flags are never reset
     uint32_t tflag_wgs = 0;  // pass-1 workgroups of the tile-flag lookup in progress (0: the shape's own count; tile_flag_geometry)
