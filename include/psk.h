@@ -118,7 +118,10 @@ int psk_device_count(int *count);
  *   "merge_single_rank"         0        1: psk_merge_* run the collective path on a one-rank communicator (tests)
  *   "lazy_clear"                1        psk_clear of a Bloom table the engine alone reads is deferred (psk_clear below); 0 = sweep at once
  *   per sketch only: "table_private" (below), read-only "window_pending_batches" (batches an update window still holds: PSK_DEVICE_BORROWED
- *   buffers among them must stay as they are).
+ *   buffers among them must stay as they are), read-only "bloom_lookup_misses" (the tally the handle's last finished large Bloom lookup
+ *   published: probes that found their bit clear in a tile-flag or keyed lookup -- a probe pass 1 tested itself because its bin or segment was
+ *   full is not among them --, keys answered absent by the return trip, gathers issued by the lazy scheme; -1 before the first.  Tile-flag
+ *   lookups publish under any "bloom_lookup" value, the other schemes under 2.  The kernels write it: synchronise the call's stream first).
  *
  * Also accepted -- where the engine switches between its kernel families, and test hooks (the tests steer small inputs onto the big-table paths
  * with them; not for callers): "partition_two_level_slices", "auto_combine_keys", "tile_threads", "even_tiles", "dense_walk_groups",

@@ -520,6 +520,10 @@ extern "C" int psk_sketch_get_option(psk_sketch *s, const char *name, int64_t *v
         *value = s->win.n ? (int64_t)s->win.batches.size() : 0;
         return PSK_OK;
     }
+    if (!strcmp(name, "bloom_lookup_misses")) {  // read-only: the miss tally the handle's last finished large lookup published (-1: none yet)
+        *value = s->lk.pin && s->lk.pin[1] ? (int64_t)s->lk.pin[0] : -1;
+        return PSK_OK;
+    }
     const OptDesc *d = opt_find(name);
     if (!d || d->ho < 0) return fail(PSK_EINVAL, "%s is not a per-sketch option", name);
     *value = s->opt[d->ho] != kHoUnset ? s->opt[d->ho] : __atomic_load_n(d->var, __ATOMIC_RELAXED);

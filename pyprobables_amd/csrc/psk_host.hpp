@@ -290,6 +290,7 @@ static inline bool part_slices(uint64_t cells, uint32_t max_shift, uint32_t min_
     g->split = g->split_idx = 0;
     g->dense = 0;
     g->append = 0;
+    g->dup_pads = 0;
     return true;
 }
 
@@ -444,6 +445,9 @@ static int launch_scatter_bins(psk_sketch *s, const Src &src, const IdxFn &idxfn
     g->segcap = (uint32_t)segcap;
     g->tile = (uint32_t)tk;
     g->dense = (mean / 6.0 + 0.5 * (double)tiles_per_wg) < (double)g_part_dense_groups ? 1u : 0u;
+    // the spare slots of a short group repeat its first probe where pass 2 only ORs or tests bits (the Bloom insert's k_bloom_apply, the tile-flag
+    // lookup's k_bloom_test_flag: PartGeom::dup_pads); a consumer that ADDS per probe (CBF unit updates, PayWeightSmall) keeps the pad value
+    g->dup_pads = (std::is_same<Pay, PayNone>::value && std::is_same<Spill, SpillBloomOr>::value) || pay_tile_tag<Pay>::value ? 1u : 0u;
     PSK_TRY(ensure(s->s_part, (uint64_t)g->nbuckets * nwg * segcap * 16 + 256));
     PSK_TRY(ensure(s->s_cnt, (uint64_t)g->nbuckets * nwg * 4 + 128));
     auto kern = k_part_bins<Src, IdxFn, Pay, Spill, KT, kBinKpt>;
@@ -523,6 +527,7 @@ static int launch_scatter_nt(psk_sketch *s, const Src &src, const IdxFn &idxfn, 
     g->tile = (uint32_t)tk;
     // pass 2's walk (for_each_batch_at): segments much shorter than a 64-lane load are walked end to end
     g->dense = (mean / Tile::GS + 0.5 * (double)tiles_per_wg) < (double)g_part_dense_groups ? 1u : 0u;
+    g->dup_pads = 0;  // (k_part_scatter pads with kPadProbe)
     PSK_TRY(ensure(s->s_part, (uint64_t)g->nbuckets * nwg * segcap * 16 + 256));
     PSK_TRY(ensure(s->s_cnt, (uint64_t)g->nbuckets * nwg * 4 + 128));  // + 12 x u64 of phase profile (dbg & 32)
     auto kern = k_part_scatter<Src, IdxFn, Pay, Spill, KT, NT>;

@@ -19,6 +19,8 @@
 // -- two barriers per tile, no scan, no second pass over the probes, no cursor / offset / delta arrays.  Same segments, same group format, same
 // segment counts as k_part_scatter, and the same probes in them: pass 2 (k_bloom_apply, k_bloom_test_flag, the nibble folds) does not know
 // which pass 1 ran.  (PayTileTag: a group's ordinal may be one ahead of a carried probe's tile, never more; k_bloom_test_flag flags both.)
+// One thing the geometry tells pass 2 (PartGeom::dup_pads, launch_scatter_bins): for the Bloom insert and the tile-flag lookup the spare slots
+// of a short group repeat its first probe instead of the pad value, so k_bloom_apply / k_bloom_test_flag take all six fields of every group.
 // Bins are `stride` words apart (cap rounded up to an even number + 2): consecutive bins start two banks apart, so that slot r of all
 // bins -- what the lanes of a wave write at about the same time -- does not sit in ONE bank.
 //
@@ -63,14 +65,17 @@ struct pay_bins_ok<PayWeightSmall> { static constexpr bool value = true; };  // 
 // byte offset, which is the address of the bin's counter AND (plus what the counter returns) of the probe's slot.
 constexpr uint32_t kBinHead = 2;  // words in front of a bin's probes
 // a group that holds nv < 6 probes (the first nv of the six slots a0 .. a2): the slots past the count read as pads -- all ones in the field, as
-// k_part_scatter leaves them (WP: the all-zero field) --, t0 / t1 = the tile's ordinal as PayTileTag spells it above the halves' counts
+// k_part_scatter leaves them (WP: the all-zero field) --, t0 / t1 = the tile's ordinal as PayTileTag spells it above the halves' counts.
+// dup (PartGeom::dup_pads: the consumer only ORs or tests bits): they repeat the group's first probe instead (nv >= 1 wherever a short group
+// is built), so that pass 2 need not look at the counts; the counts are what they are either way
 template <bool WP>
-__device__ __forceinline__ uint4 bin_short_group(const uint2 a0, const uint2 a1, const uint2 a2, uint32_t nv, uint32_t mask, uint32_t t0, uint32_t t1)
+__device__ __forceinline__ uint4 bin_short_group(const uint2 a0, const uint2 a1, const uint2 a2, uint32_t nv, uint32_t mask, uint32_t t0, uint32_t t1, bool dup)
 {
     uint32_t f[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y};
+    const uint32_t fill = WP ? 0u : (dup ? f[0] : mask);
 #pragma unroll
     for (int x = 1; x < 6; ++x)
-        if ((uint32_t)x >= nv) f[x] = WP ? 0u : mask;
+        if ((uint32_t)x >= nv) f[x] = fill;
     const uint32_t n0 = nv < 3u ? nv : 3u, n1 = nv - n0;
     uint4 o;
     o.x = f[0] | (f[1] << 20);
@@ -90,6 +95,7 @@ __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src
     constexpr bool kExactK = KT != 8;
     const uint32_t k = kExactK ? (uint32_t)KT : g.k;
     const uint32_t mask = (1u << g.shift) - 1;
+    const bool dup = g.dup_pads != 0;  // (uniform) what fills the spare slots of a short group: bin_short_group
     const uint32_t tk = g.tile;
     const uint32_t ntiles = (n + tk - 1) / tk;
     const uint32_t last = n ? n - 1 : 0;
@@ -294,7 +300,7 @@ __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src
                     if (!(dbg & 1)) out[gq] = o;
                 }
                 if constexpr (pay_tile_tag<Pay>::value) {
-                    if (tail && sub == 0 && !(dbg & 1)) out[0] = bin_short_group<WP>(e[0], e[1], e[2], rem, mask, t0, t1);
+                    if (tail && sub == 0 && !(dbg & 1)) out[0] = bin_short_group<WP>(e[0], e[1], e[2], rem, mask, t0, t1, dup);
                 }
                 if (rem && whole && sub == (whole & (L - 1))) {  // the remainder moves to the bin's first slots (whole == 0: it is there)
                     // the lanes that share a slice are neighbours in ONE wave, and a wave's LDS operations complete in order: these stores
@@ -313,7 +319,7 @@ __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src
                     const uint2 a0 = e[3 * gq], a1 = e[3 * gq + 1], a2 = e[3 * gq + 2];
                     const uint32_t left = c - 6u * gq, nv = left < 6u ? left : 6u;
                     if (cur[s] + gq < g.segcap) {
-                        out[gq] = bin_short_group<WP>(a0, a1, a2, nv, mask, t0, t1);
+                        out[gq] = bin_short_group<WP>(a0, a1, a2, nv, mask, t0, t1, dup);
                     } else {
                         const uint32_t f[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y};
 #pragma unroll
@@ -355,7 +361,7 @@ __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src
             const uint2 *e = reinterpret_cast<const uint2 *>(lds + myb[s] * stride4 + kBinHead * 4u);
             const uint2 a0 = e[0], a1 = e[1], a2 = e[2];
             if (cur[s] < g.segcap) {
-                if (!(dbg & 1)) seg[s][cur[s]] = bin_short_group<WP>(a0, a1, a2, carry[s], mask, t0, t1);
+                if (!(dbg & 1)) seg[s][cur[s]] = bin_short_group<WP>(a0, a1, a2, carry[s], mask, t0, t1, dup);
             } else {  // the segment is full: the exact fallback
                 const uint32_t f[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y};
 #pragma unroll

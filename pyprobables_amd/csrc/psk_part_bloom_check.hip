@@ -172,6 +172,19 @@ static bool tile_flag_geometry(psk_sketch *s, const Batch &b, PartGeom *g, uint6
     return true;
 }
 
+// the device word the pass-2 kernels tally their misses in, and the pinned page a call's last kernel publishes it to (psk_sketch::lk)
+static int ensure_lookup_tally(psk_sketch *s, hipStream_t st)
+{
+    if (s->lk.dev) return PSK_OK;
+    HIP_TRY(hipMalloc((void **)&s->lk.dev, 8));
+    void *pin = nullptr;
+    HIP_TRY(hipHostMalloc(&pin, 64, hipHostMallocDefault));  // [0..3] written by the device (psk_sketch::lk), [4] [5] host-only (lazy gathers, choose_scheme)
+    s->lk.pin = (volatile unsigned long long *)pin;
+    for (int e = 0; e < 8; ++e) s->lk.pin[e] = 0;
+    HIP_TRY(hipMemsetAsync(s->lk.dev, 0, 8, st));  // once: the publishing kernel re-zeroes the tally at the end of every call
+    return PSK_OK;
+}
+
 // the tile flags proper start 16 bytes into s_tflag: the word in front of them (tileflag[-1]) tells k_bloom_flag_resolve whether any is set
 static uint32_t *tflag_base(psk_sketch *s) { return (uint32_t *)s->s_tflag.p + 4; }
 constexpr uint32_t kResolveWgs = 256;
@@ -204,6 +217,9 @@ static int tile_flag_scatter(psk_sketch *s, const Batch &sub, uint64_t cnt, bool
 static int tile_flag_test(psk_sketch *s, const Batch &sub, uint64_t cnt, const PartGeom &g, uint32_t gen, uint8_t *out, unsigned long long publish_units, hipStream_t st)
 {
     bool handled = false;
+    // (the tally exists under a forced scheme too: the handle's read-only option "bloom_lookup_misses" reports it; the scheme choice reads
+    // the page only under "bloom_lookup" = 2)
+    PSK_TRY(ensure_lookup_tally(s, st));
     PSK_TRY(with_part_source(sub, &handled, [&](auto src) {
         using Src = decltype(src);
         uint32_t *tflag = tflag_base(s);
@@ -214,7 +230,7 @@ static int tile_flag_test(psk_sketch *s, const Batch &sub, uint64_t cnt, const P
         HIP_TRY(hipGetLastError());
         const uint64_t ntiles = (cnt + g.tile - 1) / g.tile;
         LookupPublish pub;
-        if (publish_units && s->eff[HO_BLOOM_LOOKUP] == 2 && s->lk.dev) pub = LookupPublish{s->lk.dev, s->lk.pin, publish_units, 3};
+        if (publish_units && s->lk.dev && s->lk.pin) pub = LookupPublish{s->lk.dev, s->lk.pin, publish_units, 3};
         // (a small grid: with no tile flagged -- the usual case of the batches this scheme is chosen for -- every workgroup leaves at once, and
         // the launch is what remains of the kernel; 1024 workgroups cost ~5 us for nothing)
         hipLaunchKernelGGL((k_bloom_flag_resolve<Src, kTuPow2>), dim3((unsigned)(ntiles < kResolveWgs ? ntiles : kResolveWgs)), dim3(kResolveThreads), 0, st, src,
@@ -337,14 +353,7 @@ static int bloom_check_lazy(psk_sketch *s, const Batch &b, uint8_t *out_dev, hip
 static int choose_scheme(psk_sketch *s, hipStream_t st)
 {
     if (s->eff[HO_BLOOM_LOOKUP] != 2) return (int)s->eff[HO_BLOOM_LOOKUP];   // forced: 0 keyed, 1 return trip, 3 tile flags, 4 lazy gathers
-    if (!s->lk.dev) {
-        HIP_TRY(hipMalloc((void **)&s->lk.dev, 8));
-        void *pin = nullptr;
-        HIP_TRY(hipHostMalloc(&pin, 64, hipHostMallocDefault));  // [0..3] written by the device (psk_sketch::lk), [4] [5] host-only (lazy gathers, below)
-        s->lk.pin = (volatile unsigned long long *)pin;
-        for (int e = 0; e < 8; ++e) s->lk.pin[e] = 0;
-        HIP_TRY(hipMemsetAsync(s->lk.dev, 0, 8, st));  // once: k_lookup_publish re-zeroes the tally at the end of every call
-    }
+    PSK_TRY(ensure_lookup_tally(s, st));
     const unsigned long long miss = s->lk.pin[0], units = s->lk.pin[1], by = s->lk.pin[2], seq = s->lk.pin[3];
     if (units) {
         const double f = (double)miss / (double)units;

@@ -72,6 +72,10 @@ struct PartGeom {
     uint32_t dense;         // pass 2: 1 = short segments, a wave walks its segments end to end (for_each_batch_at); set by pass 1's launcher
     uint32_t append;        // pass 1: 1 = my segments already hold segcnt[] groups from earlier launches with the SAME geometry -- append behind
                             // them (write-combined updates: every batch is scattered when it is handed over, pass 2 runs once per flush)
+    uint32_t dup_pads;      // 1 = the slots of a short 6 x 20-bit group past its counts hold a COPY of the group's first probe, not the pad
+                            // value: the consumer only ORs or tests bits, so it may take all six fields of every group it loaded
+                            // (k_bloom_apply, k_bloom_test_flag).  Set by launch_scatter_bins for the Bloom insert and the tile-flag lookup
+                            // only; the counts are written either way
 };
 
 // Where segment (slice b, workgroup wg) lives in the bucket buffer.  Workgroup-major: the B runs a workgroup
@@ -402,6 +406,22 @@ struct SpillBloomFlag {  // PayTileTag probe of an overflowing segment: test it 
 // s_waitcnt vmcnt(0): every barrier of pass 1 would then drain the key prefetch (a full HBM latency per tile)
 // and the previous tile's write-out stores.  Pass 1 exchanges data between waves through LDS only.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// The dynamic-LDS slice image of pass 2, addressed by BYTE OFFSET.  `smem[i]` makes every address "symbol + offset", and the symbol's value
+// reaches the instruction stream as a v_add_u32 v, 0, v per probe (the image is the kernel's only LDS: it starts at 0, but the compiler adds the
+// relocated base all the same).  A kernel that uses these helpers has no static __shared__ data and says so with lds_image_at_zero() once.
+typedef __attribute__((address_space(3))) uint32_t lds_u32_t;
+__device__ __forceinline__ void lds_image_at_zero()
+{
+    if (__builtin_amdgcn_groupstaticsize() != 0) __builtin_trap();  // (a constant: the test folds away)
+}
+__device__ __forceinline__ uint32_t lds_word_at(uint32_t byte_off) { return *reinterpret_cast<const lds_u32_t *>(byte_off); }
+__device__ __forceinline__ void lds_or_at(uint32_t byte_off, uint32_t bits)  // ds_or_b32
+{
+    (void)__hip_atomic_fetch_or(reinterpret_cast<lds_u32_t *>(byte_off), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// byte offset of the image word that holds bit (x & 0xFFFFF) of the slice: x = a 20-bit field moved down to bit 0, whatever lies above it
+__device__ __forceinline__ uint32_t lds_word_of_bit(uint32_t x) { return (x >> 3) & 0x1FFFCu; }
 
 // wave64 inclusive prefix sum on the DPP network (row_shr 1/2/4/8 inside each row of 16, then row_bcast 15 / 31 across
 // rows): 6 dependent VALU adds instead of 6 ds_bpermute round trips through the LDS pipe
@@ -1246,6 +1266,8 @@ __global__ __launch_bounds__(kSplitThreads) void k_part_split(PartGeom g1, const
 // ------------------------------------------------------------------------------------ pass 2
 constexpr int kApplyThreads = 1024;
 constexpr int kApplyWaves = kApplyThreads / 64;
+// my wave's number inside the workgroup as a SCALAR (threadIdx.x >> 6 is the same for every lane, but the compiler keeps it in a VGPR)
+__device__ __forceinline__ uint32_t wave_uniform() { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
 // Walk the groups of slice `b`: wave w takes segments w, w+16, ... (<= 64 of them: one count per lane).
 // A segment is a few hundred probes, so walking segment by segment is a chain of dependent HBM latencies
@@ -1275,7 +1297,9 @@ __device__ __forceinline__ uint32_t lane_segment_count(const uint32_t *segcnt, c
     return lane < nseg ? segcnt[(uint64_t)b * g.nwg + s0 + S * (wave + kApplyWaves * lane)] : 0u;
 }
 
-template <int D, class Body>
+// SBASE: the chunked walk forms a load's segment base on the scalar unit (below).  The Bloom kernels ask for it; the counter kernels do not:
+// their step measured 0.4 % slower with it (profiles/pass2_lean_bench_ab.txt, cfg 3), so they keep the per-lane address.
+template <int D, bool SBASE = false, class Body>
 __device__ __forceinline__ void for_each_batch_at(const uint4 *buckets, const uint32_t *segcnt, const PartGeom &g, uint32_t b,
                                                   const uint4 pad, Body body, uint32_t mycnt_pre = ~0u)
 {
@@ -1318,6 +1342,10 @@ __device__ __forceinline__ void for_each_batch_at(const uint4 *buckets, const ui
         }
         return;
     }
+    // chunked: every lane of a load reads ONE segment, so the segment's base is scalar work -- the wave number through readfirstlane (as
+    // threadIdx.x >> 6 it lives in a VGPR and drags wg, the 64-bit seg_index x segcap product and the pointer sum into the VALU, ~16
+    // instructions per load) -- and the load takes that scalar base plus the lane's 32-bit byte offset (v < cnt <= segcap < 2^24)
+    const uint32_t wave_s = SBASE ? wave_uniform() : wave;
     const uint32_t chunks = (mycnt + 63) >> 6;
     const uint32_t incl = wave_inclusive_scan(chunks), excl = incl - chunks;
     const uint32_t C = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
@@ -1332,12 +1360,14 @@ __device__ __forceinline__ void for_each_batch_at(const uint4 *buckets, const ui
             const uint32_t sl = seg < 64 ? seg : 63;
             const uint32_t v = (cc - (uint32_t)__builtin_amdgcn_readlane((int)excl, sl)) * 64 + lane;
             const uint32_t cnt = seg < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)mycnt, sl) : 0;
-            wg[d] = s0 + S * (wave + kApplyWaves * sl);
+            wg[d] = s0 + S * (wave_s + kApplyWaves * sl);
             const uint64_t base = seg_index(g, b, wg[d]) * g.segcap;
+            const char *src = reinterpret_cast<const char *>(buckets + base);
             q[d] = pad;
             at[d] = ~0ULL;
             if (v < cnt) {
-                q[d] = buckets[base + v];
+                if constexpr (SBASE) q[d] = *reinterpret_cast<const uint4 *>(src + (v << 4));
+                else q[d] = buckets[base + v];
                 at[d] = base + v;
             }
         }
@@ -1345,7 +1375,7 @@ __device__ __forceinline__ void for_each_batch_at(const uint4 *buckets, const ui
     }
 }
 
-template <int D, class Body>
+template <int D, bool SBASE = false, class Body>
 __device__ __forceinline__ void for_each_batch(const uint4 *buckets, const uint32_t *segcnt, const PartGeom &g, uint32_t b,
                                                const uint4 pad, Body body)
 {
@@ -1381,6 +1411,7 @@ __device__ __forceinline__ void for_each_batch(const uint4 *buckets, const uint3
         }
         return;
     }
+    const uint32_t wave_s = SBASE ? wave_uniform() : wave;  // (the segment's base on the scalar unit: see for_each_batch_at)
     const uint32_t chunks = (mycnt + 63) >> 6;
     const uint32_t incl = wave_inclusive_scan(chunks), excl = incl - chunks;
     const uint32_t C = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
@@ -1393,9 +1424,12 @@ __device__ __forceinline__ void for_each_batch(const uint4 *buckets, const uint3
             const uint32_t sl = seg < 64 ? seg : 63;
             const uint32_t v = (cc - (uint32_t)__builtin_amdgcn_readlane((int)excl, sl)) * 64 + lane;
             const uint32_t cnt = seg < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)mycnt, sl) : 0;
-            const uint4 *src = buckets + seg_index(g, b, wave + kApplyWaves * sl) * g.segcap;
+            const uint4 *src = buckets + seg_index(g, b, wave_s + kApplyWaves * sl) * g.segcap;
             q[d] = pad;
-            if (v < cnt) q[d] = src[v];
+            if (v < cnt) {
+                if constexpr (SBASE) q[d] = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(src) + (v << 4));
+                else q[d] = src[v];
+            }
         }
         body(q);
     }
@@ -1448,11 +1482,11 @@ __device__ __forceinline__ void load_slice(uint32_t *smem, const uint32_t *tab, 
 }
 
 // consumers that only issue LDS atomics: one callback per group
-template <int DEPTH = kApplyDepth, class F4>
+template <int DEPTH = kApplyDepth, bool SBASE = false, class F4>
 __device__ __forceinline__ void for_each_group(const uint4 *buckets, const uint32_t *segcnt, const PartGeom &g, uint32_t b,
                                                const uint4 pad, F4 f4)
 {
-    for_each_batch<DEPTH>(buckets, segcnt, g, b, pad, [&](const uint4 (&q)[DEPTH]) {
+    for_each_batch<DEPTH, SBASE>(buckets, segcnt, g, b, pad, [&](const uint4 (&q)[DEPTH]) {
 #pragma unroll
         for (int d = 0; d < DEPTH; ++d) f4(q[d]);
     });
@@ -1496,15 +1530,34 @@ static __global__ __launch_bounds__(kApplyThreads) void k_bloom_apply(uint32_t *
     const uint32_t slice_words = 1u << (g.shift - 5);
     for (uint32_t w = threadIdx.x; w < slice_words; w += kApplyThreads) smem[w] = 0;
     __syncthreads();
+    lds_image_at_zero();
     // group = two 64-bit halves of 3 x 20-bit slice-local bit indices, valid count in bits 60..63
     auto half = [&](uint32_t lo, uint32_t hi) {
-        const unsigned long long h = ((unsigned long long)hi << 32) | lo;
         const uint32_t nv = hi >> 28;
-        if (nv > 0) { const uint32_t x = (uint32_t)h & 0xFFFFFu; atomicOr(&smem[x >> 5], 1u << (x & 31)); }  // ds_or_b32
-        if (nv > 1) { const uint32_t x = (uint32_t)(h >> 20) & 0xFFFFFu; atomicOr(&smem[x >> 5], 1u << (x & 31)); }
-        if (nv > 2) { const uint32_t x = (uint32_t)(h >> 40) & 0xFFFFFu; atomicOr(&smem[x >> 5], 1u << (x & 31)); }
+        const uint32_t x0 = lo, x1 = __builtin_amdgcn_alignbit(hi, lo, 20), x2 = hi >> 8;  // the three fields at bit 0
+        if (nv > 0) lds_or_at(lds_word_of_bit(x0), 1u << (x0 & 31));  // ds_or_b32
+        if (nv > 1) lds_or_at(lds_word_of_bit(x1), 1u << (x1 & 31));
+        if (nv > 2) lds_or_at(lds_word_of_bit(x2), 1u << (x2 & 31));
     };
-    for_each_group(buckets, segcnt, g, b, make_uint4(0, 0, 0, 0), [&](const uint4 q) { half(q.x, q.y); half(q.z, q.w); });
+    if (g.dup_pads) {
+        // no slot of a group holds anything but a probe of the slice (a short group repeats its first one, and an OR of the same bit twice
+        // changes nothing): ONE predicate per group -- "this lane loaded one": a group's first half counts at least one probe, the absent
+        // group is all zero -- and six ds_or_b32 in a row under it, instead of a compare, a save-exec and an out-of-line body per probe
+        for_each_group<kApplyDepth, true>(buckets, segcnt, g, b, make_uint4(0, 0, 0, 0), [&](const uint4 q) {
+            if (q.y & 0x30000000u) {
+                const uint32_t x1 = __builtin_amdgcn_alignbit(q.y, q.x, 20), x2 = q.y >> 8;
+                const uint32_t x4 = __builtin_amdgcn_alignbit(q.w, q.z, 20), x5 = q.w >> 8;
+                lds_or_at(lds_word_of_bit(q.x), 1u << (q.x & 31));
+                lds_or_at(lds_word_of_bit(x1), 1u << (x1 & 31));
+                lds_or_at(lds_word_of_bit(x2), 1u << (x2 & 31));
+                lds_or_at(lds_word_of_bit(q.z), 1u << (q.z & 31));
+                lds_or_at(lds_word_of_bit(x4), 1u << (x4 & 31));
+                lds_or_at(lds_word_of_bit(x5), 1u << (x5 & 31));
+            }
+        });
+    } else {
+        for_each_group<kApplyDepth, true>(buckets, segcnt, g, b, make_uint4(0, 0, 0, 0), [&](const uint4 q) { half(q.x, q.y); half(q.z, q.w); });
+    }
     uint32_t spilled = 0;  // (store mode) the length of pass 1's spill list: read ONCE, in front of the barrier the list's reset waits behind
     if (sm.on) {
         spilled = sm.spill[0];
@@ -1613,14 +1666,17 @@ static __global__ __launch_bounds__(kApplyThreads) void k_bloom_test(const uint3
     if (!(dbg & 128)) load_slice(smem, tab, tab_words, w0, slice_words);
     __syncthreads();
     const uint32_t kmask = (1u << (31 - g.shift)) - 1;
-    for_each_batch_at<kApplyDepth>(buckets, segcnt, g, b, make_uint4(0, 0, 0, 0), [&](const uint4 (&q)[kApplyDepth], const uint64_t (&at)[kApplyDepth],
+    lds_image_at_zero();
+    const uint32_t wmask4 = (mask >> 5) << 2;  // ((x & mask) >> 5) * 4 == (x >> 3) & wmask4: the byte offset of a probe's image word
+    for_each_batch_at<kApplyDepth, true>(buckets, segcnt, g, b, make_uint4(0, 0, 0, 0), [&](const uint4 (&q)[kApplyDepth], const uint64_t (&at)[kApplyDepth],
                                                                                      const uint32_t (&wg)[kApplyDepth]) {
         // the LDS reads of the whole batch first (no control dependence: they issue back to back), then the tests
         uint4 w[kApplyDepth];
 #pragma unroll
         for (int d = 0; d < kApplyDepth; ++d) {
             if (dbg & 64) { w[d] = make_uint4(~0u, ~0u, ~0u, ~0u); continue; }
-            w[d] = make_uint4(smem[(q[d].x & mask) >> 5], smem[(q[d].y & mask) >> 5], smem[(q[d].z & mask) >> 5], smem[(q[d].w & mask) >> 5]);
+            w[d] = make_uint4(lds_word_at((q[d].x >> 3) & wmask4), lds_word_at((q[d].y >> 3) & wmask4), lds_word_at((q[d].z >> 3) & wmask4),
+                              lds_word_at((q[d].w >> 3) & wmask4));
         }
 #pragma unroll
         for (int d = 0; d < kApplyDepth; ++d) {  // the rare miss stores
@@ -1690,40 +1746,76 @@ static __global__ __launch_bounds__(kApplyThreads) void k_bloom_test_flag(const 
     const uint32_t mycnt = lane_segment_count(segcnt, g, b);  // (requested before the slice: see lane_segment_count)
     load_slice(smem, tab, tab_words, w0, slice_words);
     __syncthreads();
-    for_each_batch_at<kFlagDepth>(buckets, segcnt, g, b, make_uint4(0, 0, 0, 0), [&](const uint4 (&q)[kFlagDepth], const uint64_t (&)[kFlagDepth],
-                                                                                   const uint32_t (&wg)[kFlagDepth]) {
-        // a pad field (all ones inside the slice) and the fields of an absent group (all zero, counts 0) address the slice: every read is safe
-        uint32_t f[kFlagDepth][6], w[kFlagDepth][6];
+    lds_image_at_zero();
+    // x[e] = field e of the group moved down to bit 0 (whatever lies above it: the word's offset and the shift count take their own bits);
+    // a pad field (all ones inside the slice) and the fields of an absent group (all zero, counts 0) address the slice: every read is safe
+    auto fields = [](const uint4 q, uint32_t (&x)[6]) {
+        x[0] = q.x;
+        x[1] = __builtin_amdgcn_alignbit(q.y, q.x, 20);
+        x[2] = q.y >> 8;
+        x[3] = q.z;
+        x[4] = __builtin_amdgcn_alignbit(q.w, q.z, 20);
+        x[5] = q.w >> 8;
+    };
+    // the group by its counts: which of its COUNTED probes found their bit clear, and the flags of their tiles
+    auto judge = [&](const uint4 q, uint32_t wgd, const uint32_t (&x)[6], const uint32_t (&w)[6]) {
+        uint32_t clear = 0;  // bit e: probe e's table bit is clear
 #pragma unroll
-        for (int d = 0; d < kFlagDepth; ++d) {
-            f[d][0] = q[d].x & 0xFFFFFu;
-            f[d][1] = __builtin_amdgcn_alignbit(q[d].y, q[d].x, 20) & 0xFFFFFu;
-            f[d][2] = (q[d].y >> 8) & 0xFFFFFu;
-            f[d][3] = q[d].z & 0xFFFFFu;
-            f[d][4] = __builtin_amdgcn_alignbit(q[d].w, q[d].z, 20) & 0xFFFFFu;
-            f[d][5] = (q[d].w >> 8) & 0xFFFFFu;
-#pragma unroll
-            for (int e = 0; e < 6; ++e) w[d][e] = smem[f[d][e] >> 5];
+        for (int e = 0; e < 6; ++e) clear |= (((w[e] >> (x[e] & 31)) & 1u) ^ 1u) << e;
+        const uint32_t n0 = (q.y >> 28) & 3u, n1 = (q.w >> 28) & 3u;
+        const uint32_t valid = ((1u << n0) - 1u) | (((1u << n1) - 1u) << 3);
+        clear &= valid;
+        if (clear) {  // rare on the batches this scheme is chosen for
+            nmiss += (uint32_t)__builtin_popcount(clear);
+            const uint32_t ordinal = (q.y >> 30) | ((q.w >> 30) << 2);
+            tileflag[ordinal * g.nwg + wgd] = gen;
+            // (k_part_bins carries a bin's remainder into the next tile's first group: the probe may be of the tile before.  One tile
+            // flagged too many costs its re-check, nothing else: k_bloom_flag_resolve is exact)
+            if (ordinal) tileflag[(ordinal - 1u) * g.nwg + wgd] = gen;
+            tileflag[-1] = gen;  // "some tile of this round is flagged" (k_bloom_flag_resolve)
         }
+    };
+    if (g.dup_pads) {
+        // Every slot of a group holds a probe of the slice (a short group repeats its first one): the six words, each shifted by its field,
+        // ANDed -- bit 0 of the result is clear exactly when a real probe found its bit clear (a copy tests what its original tests).  Such
+        // a group, if this lane loaded it (its first half then counts at least one probe; the absent group is all zero), is judged by its
+        // counts as ever: a copy that misses is not counted twice.  No per-probe extraction of the bit, no counts, no masks on the way there.
+        for_each_batch_at<kFlagDepth, true>(buckets, segcnt, g, b, make_uint4(0, 0, 0, 0), [&](const uint4 (&q)[kFlagDepth], const uint64_t (&)[kFlagDepth],
+                                                                                       const uint32_t (&wg)[kFlagDepth]) {
+            uint32_t w[kFlagDepth][6];
 #pragma unroll
-        for (int d = 0; d < kFlagDepth; ++d) {
-            uint32_t clear = 0;  // bit e: probe e's table bit is clear
+            for (int d = 0; d < kFlagDepth; ++d) {
+                uint32_t x[6];
+                fields(q[d], x);
 #pragma unroll
-            for (int e = 0; e < 6; ++e) clear |= (((w[d][e] >> (f[d][e] & 31)) & 1u) ^ 1u) << e;
-            const uint32_t n0 = (q[d].y >> 28) & 3u, n1 = (q[d].w >> 28) & 3u;
-            const uint32_t valid = ((1u << n0) - 1u) | (((1u << n1) - 1u) << 3);
-            clear &= valid;
-            if (clear) {  // rare on the batches this scheme is chosen for
-                nmiss += (uint32_t)__builtin_popcount(clear);
-                const uint32_t ordinal = (q[d].y >> 30) | ((q[d].w >> 30) << 2);
-                tileflag[ordinal * g.nwg + wg[d]] = gen;
-                // (k_part_bins carries a bin's remainder into the next tile's first group: the probe may be of the tile before.  One tile
-                // flagged too many costs its re-check, nothing else: k_bloom_flag_resolve is exact)
-                if (ordinal) tileflag[(ordinal - 1u) * g.nwg + wg[d]] = gen;
-                tileflag[-1] = gen;  // "some tile of this round is flagged" (k_bloom_flag_resolve)
+                for (int e = 0; e < 6; ++e) w[d][e] = lds_word_at(lds_word_of_bit(x[e]));
             }
-        }
-    }, mycnt);
+#pragma unroll
+            for (int d = 0; d < kFlagDepth; ++d) {
+                uint32_t x[6];
+                fields(q[d], x);
+                uint32_t all = ~0u;
+#pragma unroll
+                for (int e = 0; e < 6; ++e) all &= w[d][e] >> (x[e] & 31);
+                if (q[d].y & 0x30000000u) {
+                    if (!(all & 1u)) judge(q[d], wg[d], x, w[d]);
+                }
+            }
+        }, mycnt);
+    } else {
+        for_each_batch_at<kFlagDepth, true>(buckets, segcnt, g, b, make_uint4(0, 0, 0, 0), [&](const uint4 (&q)[kFlagDepth], const uint64_t (&)[kFlagDepth],
+                                                                                       const uint32_t (&wg)[kFlagDepth]) {
+            uint32_t x[kFlagDepth][6], w[kFlagDepth][6];
+#pragma unroll
+            for (int d = 0; d < kFlagDepth; ++d) {
+                fields(q[d], x[d]);
+#pragma unroll
+                for (int e = 0; e < 6; ++e) w[d][e] = lds_word_at(lds_word_of_bit(x[d][e]));
+            }
+#pragma unroll
+            for (int d = 0; d < kFlagDepth; ++d) judge(q[d], wg[d], x[d], w[d]);
+        }, mycnt);
+    }
     if (miss_ctr) {  // one atomic per workgroup
         for (int o = 32; o > 0; o >>= 1) nmiss += __shfl_down(nmiss, o);
         __syncthreads();
