@@ -380,7 +380,14 @@ int psk_digest_chain(int algo, int layout, const void *data, const uint64_t *off
  *              of the remaining set, repaired in place cluster by cluster (DESIGN.md "Quotient filter: removal"); absent hashes are no-ops.
  *              scratch_dev: 2 * words + 2 + n uint32 whose first 2 * words + 2 are ZERO on entry and zero again when the call has run (one
  *              allocation serves every call on the table); *removed_dev receives the number of hashes taken out.  The reference's
- *              `_elements_added` is not decremented by a removal: that counter is the caller's.  Enqueue only. */
+ *              `_elements_added` is not decremented by a removal: that counter is the caller's.  Enqueue only.
+ *   add_alt    `for h in hashes: add_alt(h)` (quotientfilter.py:154-166, _add :355-394) for n SORTED DISTINCT device hashes into a loaded table
+ *              with q >= 5, auto-expansion left to the caller: the table of the union, each touched region rewritten in place (DESIGN.md
+ *              "Quotient filter: insertion in place"); hashes already in the table are no-ops.  result_dev[0] receives the number added,
+ *              result_dev[1] a status: 0 = the table holds the union, non-zero = the union does not fit (or fills the table so that one
+ *              region comes round to its own start) and NOTHING was written: rebuild, or raise.  scratch_dev: 2 * words + 2 + n uint32 whose
+ *              first 2 * words + 2 are ZERO on entry and zero again when the call has run -- remove_alt's layout: one allocation serves both.
+ *              Work is proportional to the regions touched.  Enqueue only. */
 int psk_qf_hash(int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, uint32_t *out,
                 int device, void *stream);
 int psk_qf_build(uint32_t q, const uint32_t *sorted_hashes_dev, uint64_t n, void *filter_dev, uint32_t *occupied_dev,
@@ -392,6 +399,8 @@ int psk_qf_check_alt(uint32_t q, const void *filter_dev, const uint32_t *occupie
                      const uint32_t *shifted_dev, const uint32_t *hashes_dev, uint64_t n, uint8_t *out_dev, int device, void *stream);
 int psk_qf_remove_alt(uint32_t q, void *filter_dev, uint32_t *occupied_dev, uint32_t *continuation_dev, uint32_t *shifted_dev,
                       const uint32_t *sorted_hashes_dev, uint64_t n, uint32_t *scratch_dev, uint32_t *removed_dev, int device, void *stream);
+int psk_qf_add_alt(uint32_t q, void *filter_dev, uint32_t *occupied_dev, uint32_t *continuation_dev, uint32_t *shifted_dev,
+                   const uint32_t *sorted_hashes_dev, uint64_t n, uint32_t *scratch_dev, uint32_t *result_dev, int device, void *stream);
 int psk_qf_decode(uint32_t q, const void *filter_dev, const uint32_t *occupied_dev, const uint32_t *continuation_dev,
                   const uint32_t *shifted_dev, int64_t *word_counts_dev, uint32_t *marks_dev, uint32_t *out_dev, uint64_t out_cap,
                   int device, void *stream);

@@ -268,6 +268,277 @@ __global__ __launch_bounds__(kBlock) void k_qf_repack(T *filter, uint32_t *occ, 
     }
 }
 
+// ---- insertion in place (psk_qf_add_alt; q >= 5; DESIGN.md "Quotient filter: insertion in place", tests/qf_insert_model.py is this code step by step)
+// Adding elements only raises positions in pos_i = max(q_i, pos_{i-1} + 1), so a new hash disturbs the table from the start b of the cluster that
+// holds its quotient's slot (the slot itself when it is empty) up to the first item that still finds its own quotient's slot free.
+//
+// k_qf_add_starts: one lane per batch hash, b into bs[].  Hashes with equal b are a group, contiguous in ring order; its leader comes first from b.
+// k_qf_add_spans:  one lane per leader, qf_walk from b as if no carry arrived there (read only).  The walk merges the old elements in slot order with the
+//                  batch hashes from the leader on by (quotient, remainder), gives each item the next free offset `nxt`, lets empty slots under the
+//                  frontier go, and stops in front of the first item whose quotient's offset is >= nxt: that item and all behind keep their place.
+//                  A hash of another group that the walk takes in sets that group's bit in `covered`: the real carry at a slot is at least this walk's.
+//                  A frontier that comes round to b is a union that does not fit: status word.
+// k_qf_add_write:  a leader nobody covered heads a region and its walk is exact.  It walks again, then writes from the end backward: from the first
+//                  new hash's offset p0 on the region is contiguous, so the items in descending order take the offsets end - 1 .. p0; the write
+//                  offset is never below the old slot being read.  An old element's quotient comes from a cursor over `occupied` that steps back at
+//                  every run start; the new hashes' occupied bits are set last, behind every read of the cursor.  Covered leaders clear their bit.
+// Lanes of the write launch share words, not bits: a lane reads its own region and the stop slot (which reads "empty or head" whatever its owner
+// does), changes metadata with atomicAnd / atomicOr gathered per word, and stores remainders to its own slots.  Every loop is bounded, every index masked.
+struct QfWalk {
+    uint32_t b, end, rend, p0, added, oc_last, pq;
+    uint64_t used;
+    bool has_pq, over;
+};
+
+__device__ __forceinline__ uint32_t qf_next_occ(const uint32_t *occ, uint32_t oc, uint32_t smask)  // the next set bit behind oc, round the ring
+{
+    const uint32_t wmask = smask >> 5, x = (oc + 1u) & smask;
+    uint32_t w = x >> 5, m = occ[w] & (0xFFFFFFFFu << (x & 31u));
+    for (uint32_t g = 0; g <= wmask && !m; ++g) {
+        w = (w + 1u) & wmask;
+        m = occ[w];
+    }
+    return m ? (w << 5) + (uint32_t)__ffs(m) - 1u : oc;
+}
+
+__device__ __forceinline__ uint32_t qf_prev_occ(const uint32_t *occ, uint32_t oc, uint32_t smask)  // the set bit before oc
+{
+    const uint32_t wmask = smask >> 5, x = (oc - 1u) & smask;
+    uint32_t w = x >> 5, m = occ[w] & (0xFFFFFFFFu >> (31u - (x & 31u)));
+    for (uint32_t g = 0; g <= wmask && !m; ++g) {
+        w = (w - 1u) & wmask;
+        m = occ[w];
+    }
+    return m ? (w << 5) + 31u - (uint32_t)__clz(m) : oc;
+}
+
+__device__ __forceinline__ bool qf_add_leader(const uint32_t *hs, const uint32_t *bs, uint64_t n, uint64_t i, uint32_t rbits)
+{
+    if (n == 1) return true;
+    const uint64_t p = i ? i - 1 : n - 1;
+    if (bs[p] != bs[i]) return true;
+    return hs[p] - (bs[p] << rbits) > hs[i] - (bs[i] << rbits);  // ring order from b: the one descent of a group that is the whole batch
+}
+
+template <class T>
+__device__ QfWalk qf_walk(const T *filter, const uint32_t *occ, const uint32_t *cont, const uint32_t *sh, uint32_t q, const uint32_t *hs, uint64_t n,
+                          const uint32_t *bs, uint64_t i0, uint32_t *covered)
+{
+    const uint32_t rbits = 32u - q, smask = (1u << q) - 1u, rmask = (1u << rbits) - 1u;
+    QfWalk w{};
+    const uint32_t b = w.b = bs[i0] & smask;
+    uint32_t ro = 0, nxt = 0, added = 0;  // offsets from b: the old slot being read, the write frontier; new hashes so far
+    uint64_t used = 0, j = i0;            // batch hashes taken in, the next one's index
+    uint32_t oc = b, oc_at = 0xFFFFFFFFu;  // the quotient of the old element at offset oc_at
+    uint32_t rw = 0xFFFFFFFFu, wo = 0, wc = 0, ws = 0, marked = 0xFFFFFFFFu;
+    w.oc_last = b;
+    bool stopped = false;
+    const uint64_t limit = 2ull * ((uint64_t)smask + 1ull) + n + 4ull;
+    for (uint64_t g = 0; g < limit; ++g) {
+        if (nxt > smask) break;  // round the ring
+        const uint32_t s = (b + ro) & smask, bit = 1u << (s & 31u);
+        if ((s >> 5) != rw) rw = s >> 5, wo = occ[rw], wc = cont[rw], ws = sh[rw];
+        const bool have_old = ((wo | ws) & bit) != 0;
+        if (!have_old && ro < nxt) {  // empty slots under the frontier each take one unit of carry: to the next slot in use of this word
+            const uint32_t above = (wo | ws) & (0xFFFFFFFFu << (s & 31u));
+            const uint32_t run = (above ? (uint32_t)__ffs(above) - 1u : 32u) - (s & 31u);
+            ro += run < nxt - ro ? run : nxt - ro;
+            continue;
+        }
+        if (have_old && oc_at != ro) {
+            if (!(wc & bit)) oc = (ws & bit) ? qf_next_occ(occ, oc, smask) : s;
+            oc_at = ro;
+        }
+        const bool have_new = used < n;
+        uint32_t nq = 0, nr = 0, bj = 0;
+        bool own = false;
+        if (have_new) {
+            const uint32_t h = hs[j];
+            nq = ((h >> rbits) - b) & smask, nr = h & rmask, bj = bs[j] & smask;
+            own = bj == b;
+        }
+        if (!have_old && !have_new) {
+            stopped = true;
+            break;
+        }
+        const uint32_t qo = (oc - b) & smask;
+        bool take_old = have_old, same = false;
+        if (have_old && have_new) {
+            if (qo != nq) take_old = qo < nq;
+            else {
+                const uint32_t orem = (uint32_t)filter[s];
+                take_old = orem < nr, same = orem == nr;
+            }
+        }
+        const uint32_t cq = (take_old || same) ? qo : nq;
+        if (cq >= nxt && !own) {
+            stopped = true;
+            break;
+        }
+        if (have_new && !take_old && covered && !own && bj != marked) {
+            atomicOr(covered + (bj >> 5), 1u << (bj & 31u));
+            marked = bj;
+        }
+        if (same) {  // the hash is in the table already
+            ++used;
+            if (++j == n) j = 0;
+            continue;
+        }
+        if (take_old) {
+            if (!added) w.pq = qo, w.has_pq = true;
+            w.oc_last = oc;
+            ++ro, ++nxt;
+            w.rend = ro;
+        } else {
+            if (!added) w.p0 = nxt;
+            ++added, ++used, ++nxt;
+            if (++j == n) j = 0;
+        }
+    }
+    w.over = !stopped;
+    w.end = nxt, w.used = used, w.added = added;
+    return w;
+}
+
+template <class T>
+__device__ void qf_write_region(T *filter, uint32_t *occ, uint32_t *cont, uint32_t *sh, uint32_t q, const uint32_t *hs, uint64_t n, uint64_t i0, const QfWalk &w)
+{
+    const uint32_t rbits = 32u - q, smask = (1u << q) - 1u, rmask = (1u << rbits) - 1u, b = w.b;
+    uint64_t k = w.used, jk = k ? (i0 + k - 1) % n : 0;  // batch hashes not yet placed, the last one's index
+    uint32_t ro = w.rend, oc = w.oc_last;
+    bool step = false;
+    uint32_t mw = 0xFFFFFFFFu, mmask = 0, mc = 0, ms = 0;  // the metadata word being written: bits decided, continuation and shifted values
+    auto flush = [&]() {
+        const uint32_t c0 = mmask & ~mc, s0 = mmask & ~ms;
+        if (c0) atomicAnd(cont + mw, ~c0);
+        if (mc) atomicOr(cont + mw, mc);
+        if (s0) atomicAnd(sh + mw, ~s0);
+        if (ms) atomicOr(sh + mw, ms);
+        mmask = mc = ms = 0;
+    };
+    auto emit = [&](uint32_t p, uint32_t qoff, uint32_t rem, bool c) {  // offsets arrive descending, each once
+        const uint32_t slot = (b + p) & smask, bit = 1u << (slot & 31u);
+        if ((slot >> 5) != mw) {
+            if (mmask) flush();
+            mw = slot >> 5;
+        }
+        mmask |= bit;
+        if (c) mc |= bit;
+        if (p != qoff) ms |= bit;
+        filter[slot] = (T)rem;
+    };
+    uint32_t rw = 0xFFFFFFFFu, wo = 0, wc = 0, ws = 0;
+    bool have_prev = false;
+    uint32_t pp = 0, pqo = 0, prem = 0;  // the item of the offset above, written once the one below it is known
+    for (uint32_t wp = w.end; wp-- > w.p0;) {
+        bool have_old = false, have_new = false, ocont = false;
+        uint32_t oq = 0, orem = 0, nq = 0, nr = 0;
+        for (uint64_t g = 0; g <= n; ++g) {
+            uint32_t s = 0, bit = 0;
+            while (ro > 0) {  // empty slots between two old clusters
+                s = (b + ro - 1u) & smask, bit = 1u << (s & 31u);
+                if ((s >> 5) != rw) rw = s >> 5, wo = occ[rw], wc = cont[rw], ws = sh[rw];
+                if ((wo | ws) & bit) break;
+                --ro;
+            }
+            have_old = ro > 0, have_new = k > 0;
+            if (have_old) {
+                if (step) oc = qf_prev_occ(occ, oc, smask), step = false;
+                oq = (oc - b) & smask, orem = (uint32_t)filter[s], ocont = (wc & bit) != 0;
+            }
+            if (have_new) {
+                const uint32_t h = hs[jk];
+                nq = ((h >> rbits) - b) & smask, nr = h & rmask;
+            }
+            if (!(have_old && have_new && oq == nq && orem == nr)) break;
+            --k;  // in the table already
+            jk = jk ? jk - 1 : n - 1;
+        }
+        if (!have_old && !have_new) break;  // (fewer items than the walk counted: not a quotient filter's table)
+        const bool take_old = have_old && (!have_new || oq > nq || (oq == nq && orem > nr));
+        const uint32_t iq = take_old ? oq : nq, irem = take_old ? orem : nr;
+        if (take_old) {
+            step = !ocont;  // a run start: the element below belongs to the occupied quotient before this one
+            --ro;
+        } else {
+            --k;
+            jk = jk ? jk - 1 : n - 1;
+        }
+        if (have_prev) emit(pp, pqo, prem, pqo == iq);
+        pp = wp, pqo = iq, prem = irem, have_prev = true;
+    }
+    if (have_prev) emit(pp, pqo, prem, w.has_pq && w.pq == pqo);
+    if (mmask) flush();
+    uint32_t ow = 0xFFFFFFFFu, ob = 0;
+    uint64_t j = i0;
+    for (uint64_t x = 0; x < w.used; ++x) {
+        const uint32_t qq = hs[j] >> rbits;
+        if ((qq >> 5) != ow) {
+            if (ob) atomicOr(occ + ow, ob);
+            ow = qq >> 5, ob = 0;
+        }
+        ob |= 1u << (qq & 31u);
+        if (++j == n) j = 0;
+    }
+    if (ob) atomicOr(occ + ow, ob);
+}
+
+__global__ __launch_bounds__(kBlock) void k_qf_add_starts(const uint32_t *occ, const uint32_t *sh, uint32_t q, const uint32_t *hs, uint64_t n, uint32_t *bs)
+{
+    const uint32_t rbits = 32u - q, smask = (1u << q) - 1u, wmask = smask >> 5;
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const uint32_t quot = hs[i] >> rbits;
+        uint32_t w = quot >> 5, start = quot;
+        if (((occ[w] | sh[w]) >> (quot & 31u)) & 1u) {  // the slot is in use: back over `shifted` to the start of its cluster
+            uint32_t upto = 0xFFFFFFFFu >> (31u - (quot & 31u));
+            for (uint32_t g = 0; g <= wmask + 1u; ++g) {
+                const uint32_t nsh = ~sh[w] & upto;
+                if (nsh) {
+                    start = (w << 5) | (31u - (uint32_t)__clz(nsh));
+                    break;
+                }
+                w = (w - 1u) & wmask;
+                upto = 0xFFFFFFFFu;
+            }
+        }
+        bs[i] = start & smask;
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_qf_add_spans(const T *filter, const uint32_t *occ, const uint32_t *cont, const uint32_t *sh, uint32_t q,
+                                                         const uint32_t *hs, uint64_t n, const uint32_t *bs, uint32_t *covered, uint32_t *result)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        if (!qf_add_leader(hs, bs, n, i, 32u - q)) continue;
+        if (qf_walk(filter, occ, cont, sh, q, hs, n, bs, i, covered).over) atomicOr(result + 1, 1u);
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_qf_add_write(T *filter, uint32_t *occ, uint32_t *cont, uint32_t *sh, uint32_t q, const uint32_t *hs, uint64_t n,
+                                                         const uint32_t *bs, uint32_t *covered, uint32_t *result)
+{
+    const uint32_t smask = (1u << q) - 1u;
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const bool refused = result[1] != 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        if (!qf_add_leader(hs, bs, n, i, 32u - q)) continue;
+        const uint32_t b = bs[i] & smask, bit = 1u << (b & 31u);
+        if (covered[b >> 5] & bit) {  // inside another group's region; the scratch goes back zeroed
+            atomicAnd(covered + (b >> 5), ~bit);
+            continue;
+        }
+        if (refused) continue;
+        const QfWalk w = qf_walk(filter, occ, cont, sh, q, hs, n, bs, i, (uint32_t *)nullptr);
+        if (w.over || !w.added) continue;
+        qf_write_region(filter, occ, cont, sh, q, hs, n, i, w);
+        atomicAdd(result, w.added);
+    }
+}
+
 // ---- decode
 // per metadata word: run starts, occupied bits, slots in use (counts[0 / 1 / 2][w]); marks[0] = the first slot with continuation = shifted = 0
 // (the anchor x above), marks[1] = the first empty slot (0xFFFFFFFF: none, the table is full)
@@ -411,6 +682,37 @@ extern "C" int psk_qf_remove_alt(uint32_t q, void *filter_dev, uint32_t *occupie
         hipLaunchKernelGGL((k_qf_repack<uint32_t>), dim3(grid), dim3(kBlock), 0, st, (uint32_t *)filter_dev, occupied_dev, continuation_dev, shifted_dev, q, dead, dirty, cursor, list, n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(cursor, 0, 4, st));
+    return PSK_OK;
+}
+
+// the table with the hashes of the batch: `for h in hashes: add_alt(h)` (quotientfilter.py:154-166, :355-394), auto-expansion left to the caller.
+// scratch_dev (uint32): the removal's layout, so that one allocation serves both -- 2 * words + 2 words that are zero on entry and zero again when the call
+// has run (the first `words` are the covered bitmap, the rest is not touched), then n cluster starts.  result_dev: added, status.
+extern "C" int psk_qf_add_alt(uint32_t q, void *filter_dev, uint32_t *occupied_dev, uint32_t *continuation_dev, uint32_t *shifted_dev,
+                              const uint32_t *sorted_hashes_dev, uint64_t n, uint32_t *scratch_dev, uint32_t *result_dev, int device, void *stream)
+{
+    PSK_TRY(check_q(q));
+    if (q < 5) return fail(PSK_EINVAL, "a table of 2^%u slots shares one metadata word between all its slots: rebuild it (psk_qf_build)", q);
+    if (!filter_dev || !occupied_dev || !continuation_dev || !shifted_dev || !result_dev) return fail(PSK_EINVAL, "NULL table pointer");
+    if (n > (1ull << 32)) return fail(PSK_EINVAL, "%llu hashes cannot be distinct", (unsigned long long)n);
+    if (n && (!sorted_hashes_dev || !scratch_dev)) return fail(PSK_EINVAL, "NULL argument");
+    PSK_USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(result_dev, 0, 8, st));
+    if (!n) return PSK_OK;
+    uint32_t *covered = scratch_dev, *bs = scratch_dev + 2ull * words_of(q) + 2;
+    const unsigned grid = grid_of(n);
+    const uint32_t rbits = 32 - q;
+    hipLaunchKernelGGL(k_qf_add_starts, dim3(grid), dim3(kBlock), 0, st, occupied_dev, shifted_dev, q, sorted_hashes_dev, n, bs);
+    auto run = [&](auto *filter) {
+        using T = std::remove_pointer_t<decltype(filter)>;
+        hipLaunchKernelGGL((k_qf_add_spans<T>), dim3(grid), dim3(kBlock), 0, st, filter, occupied_dev, continuation_dev, shifted_dev, q, sorted_hashes_dev, n, bs, covered, result_dev);
+        hipLaunchKernelGGL((k_qf_add_write<T>), dim3(grid), dim3(kBlock), 0, st, filter, occupied_dev, continuation_dev, shifted_dev, q, sorted_hashes_dev, n, bs, covered, result_dev);
+    };
+    if (rbits <= 8) run((uint8_t *)filter_dev);
+    else if (rbits <= 16) run((uint16_t *)filter_dev);
+    else run((uint32_t *)filter_dev);
+    HIP_TRY(hipGetLastError());
     return PSK_OK;
 }
 

@@ -5,7 +5,9 @@ remainder and the runs of a cluster in quotient order, so its four arrays -- ``_
 ``_is_shifted`` -- are a function of the SET of 32-bit hashes it holds, not of their order.  That makes a bulk build exact: sort and
 deduplicate the hashes (torch: rocPRIM's radix sort), place them with one prefix-max scan (``psk_qf_build``), and the table is the
 reference's bit for bit (DESIGN.md "Quotient filter"; tests/test_quotient_model.py ties the layout rule to the live reference).
-Adding to a non-empty filter is decode + concatenate + sort/unique + rebuild, exact for the same reason.
+Adding a batch to a loaded filter is exact for the same reason however it is carried out: by rewriting the touched regions in place
+(``psk_qf_add_alt``, DESIGN.md "Quotient filter: insertion in place") when the quotient stays and an empty slot remains, or by
+decode + concatenate + sort/unique + rebuild (an empty filter, q < 5, a stream that reaches the load threshold, a batch that fills the table).
 
 Removal is a batch call, ``remove_many`` / ``remove_alt_many``: the reference's ``remove_alt`` leaves the canonical table of the remaining set
 whenever the table has an empty slot (tests/test_quotient_remove_model.py), so a batch is exact however it is carried out -- by repairing the
@@ -23,7 +25,7 @@ Deviations from the reference, all deliberate:
 * ``get_hashes()`` of a completely full table returns the hashes in ascending order (the reference's walk to the first empty slot
   runs off the table there).
 
-Per-key ``add`` rebuilds the table: this class is for batches (``add_many`` / ``check_many``).
+Per-key ``add`` goes the batch's way with a batch of one: this class is for batches (``add_many`` / ``check_many``).
 """
 
 from __future__ import annotations
@@ -51,6 +53,20 @@ _I32_MIN = -(2**31)
 #   q = 20 (839 K held)   in place 0.27 ms at 2^10, 0.44 ms at 2^18 (0.31 of held), 0.59 ms at 2^19 (0.62); the rebuild 0.48 - 0.58 ms
 # In place wins up to 0.31 of held at both sizes (by 1.7 x and 1.2 x there) and ties at 0.62 at q = 20; the constant lies between the two.
 REMOVE_LOCAL_MAX_FRACTION = 0.5
+# ``_add_policy = "auto"``: a stream of up to this fraction of the hashes held, into a table of at least 2^ADD_LOCAL_MIN_QUOTIENT slots, is inserted
+# in place; anything else rebuilds the table.  profiles/quotient_add_bench.txt (scripts/bench_quotient_add.py; load 0.8, end to end, m new hashes):
+#   q = 24 (13.4 M held)  in place 0.49 ms at m = 2^10, 0.85 ms at 2^16, 1.5 ms at 2^19, 2.8 ms at 2^20 (0.078 of held), 9.7 ms at 2^21 (0.156);
+#                         the rebuild 3.5 - 3.6 ms at every m: in place wins by 7.1 x at 2^10 and 1.3 x at 2^20, and loses (0.38 x) at 2^21
+#   q = 22 (3.36 M held)  in place 0.62 ms at 2^10, 0.94 ms at 2^16 (0.020 of held), 1.10 ms at 2^17 (0.039), 4.8 ms at 2^19; the rebuild
+#                         1.02 - 1.07 ms: in place wins by 1.65 x at 2^10 and 1.10 x at 2^16, and loses (0.94 x) at 2^17
+#   q = 20 (839 K held)   in place 0.82 ms at 2^10 .. 2^14, 1.07 ms at 2^16, 2.9 ms at 2^17; the rebuild 0.54 - 0.56 ms: in place never wins --
+#                         its kernels alone take 0.46 ms for 2^10 hashes (three dependent launches, each as long as its longest walk), which is
+#                         what decoding and rebuilding 2^20 slots costs
+# (m stops at 0.8 * 2^q + m < 2^q: 2^22 new hashes do not fit a table of 2^24 slots at load 0.8.)  The crossover is not one fraction: it lies
+# between 0.078 and 0.156 of held at q = 24 and between 0.020 and 0.039 at q = 22.  The constant sits in the smaller table's bracket, which is a
+# win at both sizes; the quotient floor is the smallest size measured at which in place wins at all.
+ADD_LOCAL_MAX_FRACTION = 0.03
+ADD_LOCAL_MIN_QUOTIENT = 22
 
 
 def _check_quotient(quotient: int) -> None:
@@ -383,11 +399,66 @@ class QuotientFilter:
         return torch.cat([s[k:], s[:k]])
 
     # ------------------------------------------------------------------ insert
+    _add_policy = "auto"  # "local": insert in place where that is possible; "rebuild": decode, merge, build; "auto": by batch size (tests force each)
+
     def _add_bits(self, bits) -> None:
         """the stream `bits` (int32 bit patterns, in order) through ``add_alt`` one after the other"""
-        m = int(bits.numel())
-        if m == 0:
+        if self._add_policy not in ("auto", "local", "rebuild"):
+            raise ValueError(f"unknown _add_policy {self._add_policy!r}")
+        if int(bits.numel()) == 0:
             return
+        # an empty filter bulk-builds; q < 5: the table's metadata is one replicated word, which the in-place kernels do not take.
+        # "auto" goes by the LENGTH of the stream (an upper bound of its distinct count, known without a sort): a long stream of few distinct
+        # hashes takes the rebuild, which costs time and nothing else
+        held = self._held
+        local = self._add_policy == "local" or (self._add_policy == "auto" and self._q >= ADD_LOCAL_MIN_QUOTIENT
+                                                and int(bits.numel()) <= held * ADD_LOCAL_MAX_FRACTION)
+        if local and held and self._q >= 5 and self._add_local(bits):
+            return
+        self._add_rebuild(bits)
+
+    def _add_local(self, bits) -> bool:
+        """in place, if the stream neither changes the quotient nor fills the table -> False: nothing was changed, the rebuild is to take it"""
+        held, stale, q = self._held, self._stale, self._q
+        batch = self._usort(bits, unique=True)
+        n = int(batch.numel())
+        limit = resize_threshold(q, self._max_load_factor) if self._auto_resize else self._size
+        if held + n + stale >= limit:
+            # close to the threshold (or the last slot): the exact count of new hashes decides, and psk_qf_check_alt gives it
+            present = torch.empty(n, dtype=torch.uint8, device=self._dev())
+            N.check(N.lib().psk_qf_check_alt(*self._table_args(), batch.data_ptr(), n, present.data_ptr(), self._device, self._stream))
+            batch = batch[present == 0]
+            n = int(batch.numel())
+            total = held + n
+            if self._auto_resize and total + stale >= limit:
+                return False  # the threshold is reached inside this stream: where decides whether the table doubles
+            plan_add(q, held, stale, [total], False)  # "insufficient space", before anything changes
+            if total >= self._size:
+                return False  # the last slot: a region may come round to its own start, the build places such a table
+            if n == 0:
+                return True
+        # (else: even if every hash of the batch is new the quotient stays and slots remain; hashes in the table already are no-ops of the kernels)
+        scratch = self._take_scratch(n)
+        result = torch.empty(2, dtype=torch.int32, device=self._dev())
+        N.check(N.lib().psk_qf_add_alt(*self._table_args(), batch.data_ptr(), n, scratch.data_ptr(), result.data_ptr(), self._device, self._stream))
+        added, status = result.tolist()
+        self._remove_scratch = scratch
+        if status:
+            return False  # refused: nothing was written
+        self._held = held + added
+        return True
+
+    def _take_scratch(self, n: int):
+        """the one scratch of the in-place kernels (2 * words + 2 + n for both), zeroed; both hand it back zeroed.  A call
+        that fails may leave bits behind: only a call that ran gives it back"""
+        words = int(self._occ.numel())
+        if self._remove_scratch is None or int(self._remove_scratch.numel()) < 2 * words + 2 + n:
+            self._remove_scratch = torch.zeros(2 * words + 2 + max(n, 1024), dtype=torch.int32, device=self._dev())
+        scratch, self._remove_scratch = self._remove_scratch, None
+        return scratch
+
+    def _add_rebuild(self, bits) -> None:
+        m = int(bits.numel())
         held, stale = self._held, self._stale
         old = self._decode()[0] if held else None
         union = self._usort(bits if old is None else torch.cat([old, bits]), unique=True)
@@ -458,11 +529,8 @@ class QuotientFilter:
 
     def _remove_local(self, gone) -> int:
         n = int(gone.numel())
-        words = int(self._occ.numel())
-        if self._remove_scratch is None or int(self._remove_scratch.numel()) < 2 * words + 2 + n:
-            self._remove_scratch = torch.zeros(2 * words + 2 + max(n, 1024), dtype=torch.int32, device=self._dev())  # the kernels hand it back zeroed
         count = torch.empty(1, dtype=torch.int32, device=self._dev())
-        scratch, self._remove_scratch = self._remove_scratch, None  # (a call that fails may leave bits behind: only a call that ran gives it back)
+        scratch = self._take_scratch(n)
         N.check(N.lib().psk_qf_remove_alt(*self._table_args(), gone.data_ptr(), n, scratch.data_ptr(), count.data_ptr(), self._device, self._stream))
         removed = int(count.item())
         self._remove_scratch = scratch
