@@ -121,7 +121,9 @@ int psk_device_count(int *count);
  *   buffers among them must stay as they are), read-only "bloom_lookup_misses" (the tally the handle's last finished large Bloom lookup
  *   published: probes that found their bit clear in a tile-flag or keyed lookup -- a probe pass 1 tested itself because its bin or segment was
  *   full is not among them --, keys answered absent by the return trip, gathers issued by the lazy scheme; -1 before the first.  Tile-flag
- *   lookups publish under any "bloom_lookup" value, the other schemes under 2.  The kernels write it: synchronise the call's stream first).
+ *   lookups publish under any "bloom_lookup" value, the other schemes under 2.  The kernels write it: synchronise the call's stream first),
+ *   read-only "pass1_bins_launches", "pass1_bins_tile_keys", "pass1_bins_workgroups" (test hooks: how many pass-1 launches of the handle went
+ *   through the LDS bins, and the keys per tile / the workgroups of the last one).
  *
  * Also accepted -- where the engine switches between its kernel families, and test hooks (the tests steer small inputs onto the big-table paths
  * with them; not for callers): "partition_two_level_slices", "auto_combine_keys", "tile_threads", "even_tiles", "dense_walk_groups",

@@ -524,6 +524,19 @@ extern "C" int psk_sketch_get_option(psk_sketch *s, const char *name, int64_t *v
         *value = s->lk.pin && s->lk.pin[1] ? (int64_t)s->lk.pin[0] : -1;
         return PSK_OK;
     }
+    // read-only: the handle's pass-1 launches through the LDS bins (k_part_bins) -- how many, and keys per tile / workgroups of the last one
+    if (!strcmp(name, "pass1_bins_launches")) {
+        *value = (int64_t)s->bins.launches;
+        return PSK_OK;
+    }
+    if (!strcmp(name, "pass1_bins_tile_keys")) {
+        *value = (int64_t)s->bins.tile;
+        return PSK_OK;
+    }
+    if (!strcmp(name, "pass1_bins_workgroups")) {
+        *value = (int64_t)s->bins.wgs;
+        return PSK_OK;
+    }
     const OptDesc *d = opt_find(name);
     if (!d || d->ho < 0) return fail(PSK_EINVAL, "%s is not a per-sketch option", name);
     *value = s->opt[d->ho] != kHoUnset ? s->opt[d->ho] : __atomic_load_n(d->var, __ATOMIC_RELAXED);

@@ -116,6 +116,10 @@ struct psk_sketch {
     DevBuf s_tflag;                            // tile-flag Bloom lookups: one uint32 per pass-1 tile of a round; "flagged" = holds the round's
     uint32_t tflag_gen = 0;                    // generation number (never 0), so the flags are never reset
     uint32_t tflag_wgs = 0;  // pass-1 workgroups of the tile-flag lookup in progress (0: the shape's own count; tile_flag_geometry)
+    struct {                 // the handle's k_part_bins launches (read-only options "pass1_bins_*": the tests size their batches by them)
+        uint32_t tile = 0, wgs = 0;  // keys per tile and workgroups of the last one
+        uint64_t launches = 0;
+    } bins;
     DevBuf s_part2, s_cnt2;                    // two-level path: bucket buffer + fill counts after the second split
     DevBuf s_merge;                            // multi-GPU merge (psk_merge_or / _sum): exchange buffers
     DevBuf s_tally;                            // weighted pass 1: (sum w, sum |w|) per workgroup, folded by k_tally_fold
@@ -455,6 +459,9 @@ static int launch_scatter_bins(psk_sketch *s, const Src &src, const IdxFn &idxfn
     hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(kBinThreads), bp.lds, st, src, idxfn, pay, spill, *g, (uint32_t)n, bp.cap, bp.stride,
                        (uint32_t *)s->s_cnt.p, (uint4 *)s->s_part.p);
     HIP_TRY(hipGetLastError());
+    s->bins.tile = g->tile;
+    s->bins.wgs = g->nwg;
+    ++s->bins.launches;
     return PSK_OK;
 }
 template <class Src, class IdxFn, class Pay, class Spill, int KT, int NT>

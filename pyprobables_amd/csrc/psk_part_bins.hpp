@@ -16,6 +16,7 @@
 //                the next tile's (a workgroup runs ~13 tiles of a 10 M-key batch: one padded group per segment, written behind the last tile,
 //                instead of one per tile and slice -- 6 % of the probe stream were pad slots) --, and set the bin's count to what it kept;
 //   barrier
+// (the next tile's keys are loaded under the hash phase into registers of their own where they fit: bins_keys_ahead below)
 // -- two barriers per tile, no scan, no second pass over the probes, no cursor / offset / delta arrays.  Same segments, same group format, same
 // segment counts as k_part_scatter, and the same probes in them: pass 2 (k_bloom_apply, k_bloom_test_flag, the nibble folds) does not know
 // which pass 1 ran.  (PayTileTag: a group's ordinal may be one ahead of a carried probe's tile, never more; k_bloom_test_flag flags both.)
@@ -56,6 +57,16 @@ template <>
 struct pay_bins_ok<PayTileTag> { static constexpr bool value = true; };
 template <>
 struct pay_bins_ok<PayWeightSmall> { static constexpr bool value = true; };  // weighted CountMinSketch adds, weights 0 .. 15 (countminsketch.py:267-288)
+
+// Which instantiations load their keys one tile ahead into a second register set (knext[] in k_part_bins: + 8 VGPRs, + 10 with weights): those
+// that still fit the 80 VGPRs of six waves per SIMD without scratch, read per instantiation in the built objects
+// (profiles/bins_keys_ahead_isa.txt) -- the exact-k kernels of the 32-bit chains (power-of-two tables) up to k = 7, weighted adds up to k = 6.
+// The run-time-k kernel (KT = 8: 76-78 VGPRs before) and the 64-bit chains (two registers per hash in flight) would spill: they keep the
+// prefetch behind the hash phase and its wait behind the write-out.
+template <class IdxFn, class Pay, int KT>
+struct bins_keys_ahead {
+    static constexpr bool value = IdxFn::lo32 && KT <= (pay_weighted_plain<Pay>::value ? 6 : 7);
+};
 
 // dynamic LDS: B bins of `stride` words: word 1 = 4 x (2 + probes in the bin) (the byte offset of the next free slot), words 2 .. 2 + cap - 1 the probes
 // (8-byte aligned: the write-out reads pairs), word 2 + cap = the slot the stores of a full bin land on; + 8 words of slack behind the last bin.
@@ -140,8 +151,16 @@ __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src
     }
     uint32_t fold = 0;  // (dbg & 2: keeps the hashes alive)
     constexpr bool WP = pay_weighted_plain<Pay>::value;  // PayWeightSmall: every probe carries its key's weight (prefetched with the key)
-    typename Src::Key kcur[KPT];
-    uint32_t wcur[WP ? KPT : 1];
+    constexpr bool kAhead = bins_keys_ahead<IdxFn, Pay, KT>::value;  // the next tile's keys in registers of their own (knext[], below)
+    // kAhead: the loads of tile t + gridDim.x are issued at the TOP of tile t's hash phase into knext[] (wnext[]: the weights that travel with
+    // them) and handed to kcur[] behind it, in front of barrier 1.  vmcnt retires loads and stores in issue order, and what is in flight at the
+    // hand-over are those loads and, older than they, the write-out stores of tile t - 1: the one wait there finds both landed a hash phase ago.
+    // Nothing waits between a tile's last segment store and barrier 2 -- the stores drain under the next tile's hashing.
+    // !kAhead: the keys are loaded into kcur[] behind the hash phase and pinned behind the write-out, where the only wait that covers them,
+    // vmcnt(0), also waits for every segment store of the tile -- one L2 round trip per tile in front of barrier 2 (cfg 2: 7 % of the step,
+    // NOTES 18), the price of staying inside the register budget.
+    typename Src::Key kcur[KPT], knext[KPT];
+    uint32_t wcur[WP ? KPT : 1], wnext[WP ? KPT : 1];
     long long tally_s = 0;            // fused weight accounting (PayWeightSmall::tally, see k_part_scatter)
     unsigned long long tally_a = 0;
     uint32_t tally_b = 0;
@@ -153,6 +172,16 @@ __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src
             kcur[q] = src.load(i < last ? i : last);  // clamped, never branched around
             if constexpr (WP) wcur[q] = pay(i < last ? i : last, 0);
         }
+        // the first tile's keys are waited for HERE, once: with loads into kcur[] still in flight at the loop's entry, hipcc waits for them by
+        // count at kcur's first use inside the loop (vmcnt(3), read in the assembly), and in every later tile that count drains the stores of
+        // the tile before
+        if constexpr (kAhead) {
+#pragma unroll
+            for (int q = 0; q < KPT; ++q) {
+                Src::pin(kcur[q]);
+                if constexpr (WP) asm volatile("" : "+v"(wcur[q]));
+            }
+        }
     }
     lds_barrier();
     if (t_lane) t_prev = __builtin_readcyclecounter();
@@ -163,6 +192,16 @@ __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src
         const uint32_t base = tile * tk;
         const uint32_t tile_end = base + tk < n ? base + tk : n;
         if constexpr (PSK_EXP_PRIO == 1) __builtin_amdgcn_s_setprio(0);
+        // ---- the next tile's keys (they land under this tile's hashing; clamped: a workgroup with no further tile loads a key that exists)
+        if constexpr (kAhead) {
+            const uint32_t nb = (tile + gridDim.x) * tk;
+#pragma unroll
+            for (int q = 0; q < KPT; ++q) {
+                const uint32_t i = nb + (uint32_t)q * NT + threadIdx.x;
+                knext[q] = src.load(i < last ? i : last);
+                if constexpr (WP) wnext[q] = pay(i < last ? i : last, 0);
+            }
+        }
         // ---- hash, take a slot, store: key after key
 #pragma unroll
         for (int q = 0; q < KPT; ++q) {
@@ -252,8 +291,18 @@ __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src
                 }
             }
         }
-        // ---- the next tile's keys (they land under the write-out)
-        {
+        // ---- the hand-over: the one wait for the next tile's keys (and, older, for the stores of the tile before: see knext[] above)
+        if constexpr (kAhead) {
+#pragma unroll
+            for (int q = 0; q < KPT; ++q) {
+                Src::pin(knext[q]);
+                kcur[q] = knext[q];
+                if constexpr (WP) {
+                    asm volatile("" : "+v"(wnext[q]));
+                    wcur[q] = wnext[q];
+                }
+            }
+        } else {
             const uint32_t nb = (tile + gridDim.x) * tk;
 #pragma unroll
             for (int q = 0; q < KPT; ++q) {
@@ -342,10 +391,12 @@ __global__ __launch_bounds__(kBinThreads, kBinMinWaves) void k_part_bins(Src src
 #pragma unroll
         for (int s = 0; s < kSlicesPerLane; ++s)
             if (myb[s] != ~0u && sub == 0) *reinterpret_cast<uint32_t *>(lds + myb[s] * stride4 + kCnt) = (kBinHead + carry[s]) * 4u;
+        if constexpr (!kAhead) {
 #pragma unroll
-        for (int q = 0; q < KPT; ++q) {
-            Src::pin(kcur[q]);
-            if constexpr (WP) asm volatile("" : "+v"(wcur[q]));
+            for (int q = 0; q < KPT; ++q) {
+                Src::pin(kcur[q]);
+                if constexpr (WP) asm volatile("" : "+v"(wcur[q]));
+            }
         }
         PSK_BIN_TICK(2);
         lds_barrier();
