@@ -34,20 +34,10 @@ static int cbf_running_chunk_t(psk_sketch *s, const CbfRunArena &a, const int32_
     HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
     HIP_TRY(hipMemsetAsync(a.tally, 0, kCbfRunTallyBytes, st));
     // (bin, e) in order of bin, arrival order inside a bin: one row of E elements
-    const uint2 *sorted = nullptr;
-    for (uint32_t p = 0; p < a.l.passes; ++p) {
-        const uint2 *src = a.pairs[(p + 1) & 1];  // (pass 0 reads a.bins, which lies there)
-        uint2 *dst = a.pairs[p & 1];
-        if (p == 0) hipLaunchKernelGGL((k_run_sort_hist<true>), dim3(tiles), dim3(64), 0, st, (const uint32_t *)a.bins, src, a.hist, E, 0u, tiles, 8 * p);
-        else hipLaunchKernelGGL((k_run_sort_hist<false>), dim3(tiles), dim3(64), 0, st, (const uint32_t *)nullptr, src, a.hist, E, 0u, tiles, 8 * p);
-        hipLaunchKernelGGL(k_run_sort_scan, dim3(1), dim3(kRunScanThreads), 0, st, a.hist, 256 * tiles);
-        if (p == 0) hipLaunchKernelGGL((k_run_sort_scatter<true>), dim3(tiles), dim3(64), 0, st, (const uint32_t *)a.bins, src, dst, (const uint32_t *)a.hist, E, 0u, tiles, 8 * p);
-        else hipLaunchKernelGGL((k_run_sort_scatter<false>), dim3(tiles), dim3(64), 0, st, (const uint32_t *)nullptr, src, dst, (const uint32_t *)a.hist, E, 0u, tiles, 8 * p);
-        sorted = dst;
-    }
+    const uint2 *sorted = segscan_sort(a.pairs, a.hist, 1, E, 0, tiles, a.l.passes, st);
     uint32_t *fin = (uint32_t *)a.pairs[a.l.passes & 1];  // (the buffer the last pass read: free from here on)
     hipLaunchKernelGGL((k_cbfr_reduce<ADDONLY>), dim3(blocks), dim3(kRunSegBlock), 0, st, sorted, w, base, E, k, a.agg);
-    hipLaunchKernelGGL(k_cbfr_carry, dim3(1), dim3(kRunScanThreads), 0, st, a.agg, blocks);
+    hipLaunchKernelGGL((k_seg_carry<CbfMap>), dim3(1), dim3(kRunScanThreads), 0, st, a.agg, blocks);
     hipLaunchKernelGGL((k_cbfr_apply<ADDONLY>), dim3(blocks), dim3(kRunSegBlock), 0, st, sorted, w, base, E, k, (const CbfMap *)a.agg, (const uint32_t *)s->table, a.before,
                        fin, flag);
     hipLaunchKernelGGL((k_cbfr_perop<ADDONLY>), dim3(opblocks), dim3(kRunSegBlock), 0, st, (const uint32_t *)a.before, w, base, n, k, out, flag, a.tally);

@@ -18,9 +18,9 @@
 //
 // Passes over one chunk of n ops, E = n * k probes, probe e = i * k + s (op-major: e is arrival order, op = e / k):
 //   k_cbfr_hash        bins[e] = h_s(key_i) % m
-//   k_run_sort_*       (psk_running.hpp) stable LSD radix sort of (bin, e): ONE row of E elements, ceil(lg m / 8) passes
-//   k_cbfr_reduce / _carry / _apply   segmented scan of maps, reduce-then-scan with a single-workgroup second level; _apply stores the
-//                      counter's value in front of the OP at before[e] and the value behind a counter's last probe at fin[j]
+//   segscan_sort       (psk_segscan.hpp) stable LSD radix sort of (bin, e): ONE row of E elements, ceil(lg m / 8) passes
+//   k_cbfr_reduce / k_seg_carry / k_cbfr_apply   segmented scan of maps, reduce-then-scan with a single-workgroup second level; _apply stores
+//                      the counter's value in front of the OP at before[e] and the value behind a counter's last probe at fin[j]
 //   k_cbfr_perop       per op: its k before-values -> out[i], the verification flag, the chunk's tallies
 //   k_cbfr_commit      the last element of every segment stores fin[j] into the table          (only after a clean verdict)
 //   k_cbfr_book        the chunk's tallies -> the handle's counters
@@ -33,33 +33,30 @@ namespace psk {
 constexpr long long kCbfNoAdd = -(1LL << 61);
 constexpr uint32_t kCbfMax = 0xFFFFFFFFu;
 
-// One stretch of the sorted run as a map: that of its LAST segment as far as the stretch covers it; head = a segment starts inside it.
+// One stretch of the sorted run as a map (the contract of a scan value: psk_segscan.hpp)
 struct CbfMap {
     long long a, p;
     uint32_t head;
-    static __device__ __forceinline__ CbfMap identity() { return CbfMap{0, kCbfNoAdd, 0u}; }
+    static __host__ __device__ __forceinline__ CbfMap identity() { return CbfMap{0, kCbfNoAdd, 0u}; }
     // an op of signed weight w that probes the counter c times (c > 1: only exact for the ops k_cbfr_apply does not flag)
-    static __device__ __forceinline__ CbfMap of(int32_t w, uint32_t c, bool head)
+    static __host__ __device__ __forceinline__ CbfMap of(int32_t w, uint32_t c, bool head)
     {
         const long long a = (long long)w * (long long)c;
         return CbfMap{a, w >= 0 ? a : kCbfNoAdd, head ? 1u : 0u};
     }
-    __device__ __forceinline__ uint32_t operator()(uint32_t x) const
+    __host__ __device__ __forceinline__ uint32_t operator()(uint32_t x) const
     {
         return (x == kCbfMax || (long long)x + p >= (long long)kCbfMax) ? kCbfMax : (uint32_t)((long long)x + a);
     }
     // b follows a
-    static __device__ __forceinline__ CbfMap combine(const CbfMap &a, const CbfMap &b)
+    static __host__ __device__ __forceinline__ CbfMap combine(const CbfMap &a, const CbfMap &b)
     {
         if (b.head) return CbfMap{b.a, b.p, 1u};
         const long long q = a.a + b.p;
         return CbfMap{a.a + b.a, a.p > q ? a.p : q, a.head};
     }
-    static __device__ __forceinline__ CbfMap shfl_up(const CbfMap &x, int o)
-    {
-        return CbfMap{__shfl_up(x.a, o), __shfl_up(x.p, o), (uint32_t)__shfl_up((int)x.head, o)};
-    }
 };
+__device__ __forceinline__ CbfMap seg_shfl_up(const CbfMap &x, int o) { return CbfMap{__shfl_up(x.a, o), __shfl_up(x.p, o), (uint32_t)__shfl_up((int)x.head, o)}; }
 
 // the signed weight of op i of the batch (nullptr: +1).  ADDONLY (psk_cbf_add_running): a negative weight can only come from a device batch
 // (the host entry refuses it before anything runs); it counts as 0 and k_cbfr_perop tallies it as a contract violation.
@@ -132,27 +129,8 @@ __global__ __launch_bounds__(kRunSegBlock) void k_cbfr_reduce(const uint2 *sorte
 {
     __shared__ CbfMap wtot[kRunSegBlock / 64];
     const CbfElem x = cbfr_load<ADDONLY>(sorted, w, base, n, k);
-    const CbfMap incl = run_block_mapscan<kRunSegBlock>(cbfr_map(x), wtot);
+    const CbfMap incl = block_scan<kRunSegBlock>(cbfr_map(x), wtot);
     if (threadIdx.x == kRunSegBlock - 1) agg[blockIdx.x] = incl;
-}
-
-// agg[b] -> what lies in front of block b (exclusive scan, in place); ONE workgroup
-static __global__ __launch_bounds__(kRunScanThreads) void k_cbfr_carry(CbfMap *a, uint32_t nblk)
-{
-    __shared__ CbfMap wtot[kRunScanThreads / 64];
-    __shared__ CbfMap all[kRunScanThreads];
-    const uint32_t per = (nblk + kRunScanThreads - 1) / kRunScanThreads;
-    const uint32_t lo = threadIdx.x * per < nblk ? threadIdx.x * per : nblk, hi = lo + per < nblk ? lo + per : nblk;
-    CbfMap mine = CbfMap::identity();
-    for (uint32_t t = lo; t < hi; ++t) mine = CbfMap::combine(mine, a[t]);
-    all[threadIdx.x] = run_block_mapscan<kRunScanThreads>(mine, wtot);
-    __syncthreads();
-    CbfMap run = threadIdx.x ? all[threadIdx.x - 1] : CbfMap::identity();
-    for (uint32_t t = lo; t < hi; ++t) {
-        const CbfMap x = a[t];
-        a[t] = run;
-        run = CbfMap::combine(run, x);
-    }
 }
 
 // before[e] = the counter's value in front of the op of probe e (the first probe of a group stores it for the whole group);
@@ -168,7 +146,7 @@ __global__ __launch_bounds__(kRunSegBlock) void k_cbfr_apply(const uint2 *sorted
     __shared__ CbfMap incl_s[kRunSegBlock];
     const CbfElem x = cbfr_load<ADDONLY>(sorted, w, base, n, k);
     const CbfMap front = carry[blockIdx.x];
-    incl_s[threadIdx.x] = CbfMap::combine(front, run_block_mapscan<kRunSegBlock>(cbfr_map(x), wtot));
+    incl_s[threadIdx.x] = CbfMap::combine(front, block_scan<kRunSegBlock>(cbfr_map(x), wtot));
     __syncthreads();
     if (!x.valid) return;
     const uint32_t j = blockIdx.x * kRunSegBlock + threadIdx.x;
@@ -199,7 +177,8 @@ template <bool ADDONLY>
 __global__ __launch_bounds__(kRunSegBlock) void k_cbfr_perop(const uint32_t *before, const int32_t *w, uint64_t base, uint32_t n, uint32_t k, uint32_t *out,
                                                              uint32_t *flag, unsigned long long *tally)
 {
-    __shared__ unsigned long long wtot[kRunSegBlock / 64];
+    using S = Sum<unsigned long long>;
+    __shared__ S wtot[kRunSegBlock / 64];
     const uint32_t i = blockIdx.x * kRunSegBlock + threadIdx.x;
     unsigned long long added = 0, removed = 0, sat = 0, viol = 0, ab = 0;
     bool bad = false;
@@ -233,9 +212,9 @@ __global__ __launch_bounds__(kRunSegBlock) void k_cbfr_perop(const uint32_t *bef
     }
     if (__ballot(bad) && (threadIdx.x & 63u) == 0) *flag = 1u;
     // (a block's sums: < 2^8 * 2^31 * 64)
-    const unsigned long long s0 = run_block_scan<kRunSegBlock>(added, wtot), s1 = run_block_scan<kRunSegBlock>(removed, wtot),
-                             s2 = run_block_scan<kRunSegBlock>(viol, wtot), s3 = run_block_scan<kRunSegBlock>(sat, wtot),
-                             s4 = run_block_scan<kRunSegBlock>(ab, wtot);
+    const unsigned long long s0 = block_scan<kRunSegBlock>(S{added}, wtot).v, s1 = block_scan<kRunSegBlock>(S{removed}, wtot).v,
+                             s2 = block_scan<kRunSegBlock>(S{viol}, wtot).v, s3 = block_scan<kRunSegBlock>(S{sat}, wtot).v,
+                             s4 = block_scan<kRunSegBlock>(S{ab}, wtot).v;
     if (threadIdx.x == kRunSegBlock - 1) {
         if (s0) atomicAdd(tally + 0, s0);
         if (s1) atomicAdd(tally + 1, s1);

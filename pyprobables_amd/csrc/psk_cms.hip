@@ -134,8 +134,8 @@ extern "C" int psk_cms_update_ordered(psk_sketch *s, int layout, const void *dat
 // countminsketch.py:267-288 for a whole ordered batch of adds: the table, elements_added and EVERY op's return value as the reference's loop
 // leaves them.  The parallel passes of psk_running.hpp wherever they apply (depth <= kMaxDepthMeanMin, width <= 2^32; weights >= 0 is the
 // entry's contract), else k_cms_ordered: always exact.  Which one ran: read-only options "cms_running_fast" / "cms_running_sequential".
-// SGN: psk_cms_update_running, :267-321 -- a negative weight removes; the same chunking, eligibility and fall-back with the signed passes,
-// counted by "cms_update_running_fast" / "cms_update_running_sequential".
+// SGN: psk_cms_update_running, :267-321 -- a negative weight removes; the same chunking, eligibility, passes and fall-back with the signed
+// algebra (RunSignedOps in place of RunAddOps), counted by "cms_update_running_fast" / "cms_update_running_sequential".
 template <bool SGN>
 static int cms_running(psk_sketch *s, int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, const int32_t *weights, int where,
                        int query, int64_t els_in, void *out, int64_t *els_out, void *stream)
@@ -169,8 +169,9 @@ static int cms_running(psk_sketch *s, int layout, const void *data, const uint64
     int64_t *els_dev = where == PSK_DEVICE && els_out ? els_out : (int64_t *)s->s_aux.p;
     if (s->k <= (uint32_t)kMaxDepthMeanMin && s->m <= (1ULL << 32)) {
         __atomic_add_fetch(SGN ? &g_update_running_fast : &g_running_fast, 1, __ATOMIC_RELAXED);
+        using Ops = std::conditional_t<SGN, RunSignedOps, RunAddOps>;
         RunArena a;
-        PSK_TRY(cms_running_arena(s, n, &a, SGN));
+        PSK_TRY(cms_running_arena<Ops>(s, n, &a));
         for (uint64_t base = 0; base < n; base += a.cap) {
             const uint32_t nc = (uint32_t)(n - base < a.cap ? n - base : a.cap);
             PSK_TRY(with_source(b, [&](auto src) {
@@ -180,7 +181,7 @@ static int cms_running(psk_sketch *s, int layout, const void *data, const uint64
                     return (int)PSK_OK;
                 });
             }));
-            PSK_TRY((SGN ? cms_running_chunk_signed : cms_running_chunk)(s, a, w, base, nc, base == 0, els_in, query, o.dev, els_dev, st));
+            PSK_TRY(cms_running_chunk<Ops>(s, a, w, base, nc, base == 0, els_in, query, o.dev, els_dev, st));
         }
     } else {  // one lane, one op after the other (int64 weights and results: widened / narrowed around it)
         __atomic_add_fetch(SGN ? &g_update_running_sequential : &g_running_sequential, 1, __ATOMIC_RELAXED);

@@ -25,7 +25,7 @@ WHERE = ("host", "device")
 QUERIES = ("min", "mean", "mean-min")
 FOOTER = struct.Struct("IIq")  # width, depth, elements_added behind the bins of an exported sketch
 I32_MAX, I32_MIN, I64_MAX = E.I32_MAX, -(2**31), E.I64_MAX
-# csrc/psk_running.hpp: kRunChunk, kRunCells, kRunSortTile, kRunSegBlock -- restated, so that a change there fails test_chunk_seams loudly
+# csrc/psk_running.hpp: kRunChunk, kRunCells; csrc/psk_segscan.hpp: kRunSortTile, kRunSegBlock -- restated, so that a change there fails test_chunk_seams loudly
 RUN_CHUNK, RUN_CELLS, RUN_SORT_TILE, RUN_SEG_BLOCK = 1 << 20, 1 << 23, 2048, 256
 
 

@@ -254,6 +254,15 @@ def test_tile_edges(pa, N, n):
         run_and_check(pa, N, width, depth, query, h, w, bins, -7, where)
 
 
+def test_more_scan_blocks_than_carry_threads(pa, N):
+    """256 * 1025 unit ops of alternating sign into one row of 4 bins: 1025 scan blocks and 1025 tiles for single-workgroup carries of 1024
+    threads, so a thread's stretch holds two items and half of the threads hold none (every other batch of this suite has fewer blocks per
+    chunk than threads); the mean-min query shows elements_added in front of every tile"""
+    n, width, depth = 256 * 1025, 4, 1
+    w = np.where(np.arange(n) % 2 == 0, 1, -1)
+    run_and_check(pa, N, width, depth, "mean-min", hashes_of(n, depth, 9, 21), w, near_rails(width * depth, 2), 5, "device")
+
+
 # ------------------------------------------------------------------ 4. chunk seams
 _seam_refs: dict = {}
 
@@ -302,7 +311,7 @@ def test_chunk_seams(pa, N, n, els0):
 
 
 def test_mean_min_across_a_chunk_seam(pa, N):
-    """elements_added after every op is carried from chunk to chunk (st[0] / st[1]): only the mean-min query shows it per op"""
+    """elements_added after every op is carried from chunk to chunk (st[0]): only the mean-min query shows it per op"""
     n, width, depth = 131072 + 300, 8, 64
     h, w = hashes_of(n, depth, 50, 9), mixed_weights(n, 9)
     w = np.where(np.abs(w) > 5, w % 7 - 3, w)
