@@ -407,6 +407,29 @@ int psk_qf_decode(uint32_t q, const void *filter_dev, const uint32_t *occupied_d
                   const uint32_t *shifted_dev, int64_t *word_counts_dev, uint32_t *marks_dev, uint32_t *out_dev, uint64_t out_cap,
                   int device, void *stream);
 
+/* --------------------------------------------------------- BloomFilterBank
+ * Many small Bloom filters of ONE geometry (m_bits, k) in one table: `filters` rows of psk_bank_row_bytes(m_bits) =
+ * psk_bloom_table_bytes(m_bits) bytes each, contiguous, bits LSB-first as in psk_bloom_add; the pad bits of a row at or beyond m_bits are
+ * never set.  Row f is, byte for byte, the table of the reference's BloomFilter after add() of the keys sent to f (bloom.py:234-272).
+ * No handle: the caller owns the (device) table; `data` / `offsets` / `ids` / `out` follow `where`, the table and seg / perm are device memory.
+ *   add    bloom.py:241-250 per row: filter ids[i] gets key i.  ids >= filters are skipped, never written.
+ *   check  out[i] = AND of the k bits of key i in row ids[i] (bloom.py:261-272); 0 for ids >= filters.
+ *   build  keys grouped by filter, device keys only: filter f gets the keys at grouped positions [seg[f], seg[f+1]); position j is key
+ *          perm[j] (perm == NULL: key j).  seg = uint64[filters + 1] on the device, non-decreasing, seg[filters] <= n.  One workgroup
+ *          per (filter, part) sets the bits in an LDS image of the row and ORs the non-zero words into the table once.
+ *          split: workgroups per filter (>= 1).  route: 0 = per part (the image unless the part is small or the row exceeds 65536 bytes),
+ *          1 = always the LDS image (rows over 65536 bytes: PSK_EINVAL), 2 = atomics straight into the row.  Enqueue only.
+ * PSK_KEYS_HASHES needs key_len >= k.  n < 2^32 per call. */
+uint64_t psk_bank_row_bytes(uint64_t m_bits);
+int psk_bank_add(void *table_dev, uint64_t filters, uint64_t m_bits, uint32_t k, int layout, const void *data, const uint64_t *offsets,
+                 uint64_t n, uint32_t key_len, int where, const uint32_t *ids, int device, void *stream);
+int psk_bank_check(const void *table_dev, uint64_t filters, uint64_t m_bits, uint32_t k, int layout, const void *data,
+                   const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, const uint32_t *ids, uint8_t *out, int device,
+                   void *stream);
+int psk_bank_build(void *table_dev, uint64_t filters, uint64_t m_bits, uint32_t k, int layout, const void *data, const uint64_t *offsets,
+                   uint64_t n, uint32_t key_len, const uint64_t *seg_dev, const uint32_t *perm_dev, uint32_t split, int route, int device,
+                   void *stream);
+
 /* ------------------------------------------------------------ CuckooFilter
  * cuckoo/cuckoo.py: `capacity` buckets of `bucket_size` fingerprints of `fp_bits` bits.  No handle: the caller owns (device memory)
  *   buckets   uint32[capacity][bucket_size], every row filled from the left, its unused slots 0 (an export is this array plus the footer)

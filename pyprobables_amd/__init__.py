@@ -6,6 +6,7 @@ Drop-in names for the accelerated path (reference ``probables/__init__.py:3-53``
 the work is done by hand-written gfx950 HIP kernels behind the C ABI in ``include/psk.h``.
 """
 
+from .bank import BloomFilterBank
 from .bloom import BloomFilter
 from .countingbloom import CountingBloomFilter
 from .countminsketch import CountMeanMinSketch, CountMeanSketch, CountMinSketch, HeavyHitters, StreamThreshold
@@ -30,6 +31,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "BloomFilter",
+    "BloomFilterBank",
     "CountingBloomFilter",
     "CountMinSketch",
     "CountMeanSketch",

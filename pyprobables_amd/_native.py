@@ -84,6 +84,10 @@ PROTOTYPES = {
     "psk_qf_remove_alt": (_int, [_u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _int, _vp]),
     "psk_qf_add_alt": (_int, [_u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _int, _vp]),
     "psk_qf_decode": (_int, [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _int, _vp]),
+    "psk_bank_row_bytes": (_u64, [_u64]),
+    "psk_bank_add": (_int, [_vp, _u64, _u64, _u32, *_KEYS, _int, _vp, _int, _vp]),
+    "psk_bank_check": (_int, [_vp, _u64, _u64, _u32, *_KEYS, _int, _vp, _vp, _int, _vp]),
+    "psk_bank_build": (_int, [_vp, _u64, _u64, _u32, *_KEYS, _vp, _vp, _u32, _int, _int, _vp]),
     "psk_ck_triples": (_int, [_u64, _u32, *_KEYS, _int, _vp, _int, _vp]),
     "psk_ck_check": (_int, [_u64, _u32, _u32, _vp, _vp, *_KEYS, _int, _vp, _int, _vp]),
     "psk_ck_present": (_int, [_u64, _u32, _vp, _vp, _vp, _u64, _vp, _int, _vp]),

@@ -1,0 +1,357 @@
+"""BloomFilterBank: thousands of small Bloom filters of ONE geometry in one device table, built and queried a batch at a time.
+
+Filter ``f`` of the bank is, byte for byte, the reference's ``BloomFilter(est_elements, false_positive_rate)`` after ``add()`` of the keys
+sent to ``f`` (``probables/blooms/bloom.py:234-272``): one filter per row group, SSTable, shard, tenant or document, without one object,
+one handle and one launch per filter.  Row ``f`` of :attr:`table_tensor` is that filter's bit array, padded to 16 bytes.
+
+Two routes lead into the table (``include/psk.h``): *direct* -- every key carries a filter id, its k probes are atomics
+into that row (``psk_bank_add``) -- and *grouped* -- the keys of a filter lie (or are sorted) together, one workgroup sets a filter's bits in
+an LDS image of the row and ORs the image into the table once (``psk_bank_build``).
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _native as N
+from ._base import _raw_stream, _resolve_device
+from .bloom import BloomFilter
+from .exceptions import NativeLibraryError, SimilarityError
+from .hashes import default_fnv_1a, device_digest, is_fused_fnv
+from .keys import KeyBatch, digest_batch, pack_hashes, pack_keys
+
+try:
+    import torch
+except Exception:  # pragma: no cover
+    torch = None
+
+# Device keys with ids take the grouped route (torch.sort of the ids + psk_bank_build) from this many keys on; None = never.  Measured
+# (scripts/bench_bank.py part (b), profiles/bank_bench.txt: 4096 filters of 11 984 bytes, random ids, one MI355X): direct atomics win up to
+# 2^20 keys (0.41 against 0.50 ms), sort + grouped from 2^21 on (0.60 against 0.69 ms; 2.3 x at 2^25).  What the sort buys is the LDS image:
+# the automatic choice also wants a mean segment that takes it (`_grouped_pays`), else the grouped route would be the same atomics behind a sort.
+BANK_GROUP_MIN_KEYS = 1 << 21
+BANK_ROUTE_R = 16           # kBankRouteR of csrc/psk_bank.hip: route 0 takes the LDS image for a part with keys * k * R >= the row's words
+BANK_LDS_ROW_BYTES = 65536  # rows beyond it never take the LDS image
+_ELEM = {N.KEYS_FIXED: 1, N.KEYS_VARLEN8: 1, N.KEYS_VARLEN32: 4, N.KEYS_HASHES: 8}
+
+
+def group_ids(ids, num_filters: int):
+    """ids[n] -> (perm uint32[n], seg uint64[num_filters + 1]): the keys of filter f, in their order of arrival, are perm[seg[f]:seg[f + 1]]
+    (what ``psk_bank_build`` takes; the device route does the same with torch.sort + searchsorted).  An id outside [0, num_filters) raises."""
+    a = np.asarray(ids)
+    if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+        raise TypeError("ids must be a 1-D integer array")
+    a = a.astype(np.int64, copy=False)
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= num_filters):
+        raise ValueError(f"filter ids must lie in [0, {num_filters})")
+    perm = np.argsort(a, kind="stable").astype(np.uint32)
+    seg = np.zeros(num_filters + 1, dtype=np.uint64)
+    np.cumsum(np.bincount(a, minlength=num_filters), out=seg[1:])
+    return perm, seg
+
+
+def _slice_batch(b: KeyBatch, lo: int, hi: int) -> KeyBatch:
+    """keys [lo, hi) of a batch, without copying the keys"""
+    if lo == 0 and hi == b.n:
+        return b
+    if b.layout in (N.KEYS_FIXED, N.KEYS_HASHES):
+        stride = b.key_len * _ELEM[b.layout]
+        return KeyBatch(b.layout, b.data + lo * stride if b.data else 0, 0, hi - lo, b.key_len, b.where, b.device, b.keep)
+    if b.where == N.DEVICE:  # device offsets are positions in the blob: they need not start at 0
+        return KeyBatch(b.layout, b.data, b.offsets + 8 * lo, hi - lo, 0, b.where, b.device, b.keep)
+    offs = np.ctypeslib.as_array((C.c_uint64 * (b.n + 1)).from_address(b.offsets))
+    o = offs[lo:hi + 1] - offs[lo]  # host blobs are staged from their first element
+    return KeyBatch(b.layout, b.data + int(offs[lo]) * _ELEM[b.layout], o.ctypes.data, hi - lo, 0, b.where, b.device, [*b.keep, o])
+
+
+class BloomFilterBank:
+    """``num_filters`` Bloom filters sized by ``(est_elements, false_positive_rate)`` as the reference sizes one (bloom.py:463-502).
+
+    Keys are accepted as everywhere in the package (lists of ``str`` / ``bytes``, ``(n, L)`` uint8 arrays or tensors, ragged
+    ``(blob, offsets)``); ``ids`` / ``filter_offsets`` are integer arrays or tensors, host or device.  A non-default ``hash_function`` is
+    evaluated on the host (the digest families on the device) and travels as pre-computed hashes, as in :class:`BloomFilter`."""
+
+    _CHUNK = 2**32 - 1  # keys per engine call
+
+    def __init__(self, num_filters, est_elements, false_positive_rate, hash_function=None, device=None):
+        if not (isinstance(num_filters, (int, np.integer)) and 0 < int(num_filters) < 2**31):
+            raise ValueError("num_filters must be an integer in [1, 2^31)")
+        L = N.lib()
+        self._fpr, self._number_hashes, self._num_bits = BloomFilter._get_optimized_params(est_elements, false_positive_rate)
+        if self._num_bits > 2**31:
+            raise ValueError("a bank's filters hold at most 2^31 bits each: use BloomFilter for big tables")
+        self._est_elements = est_elements
+        self._num_filters = int(num_filters)
+        self._hash_arg = hash_function
+        self._hash_func = default_fnv_1a if hash_function is None else hash_function
+        self._is_fused = is_fused_fnv(hash_function)
+        self._digest = device_digest(self._hash_func)
+        self._row_bytes = int(L.psk_bank_row_bytes(self._num_bits))
+        if N.device_count() == 0 or torch is None or not torch.cuda.is_available():
+            raise NativeLibraryError("no HIP device available: the bank's table lives in GPU memory and there is no CPU fallback")
+        self._device = _resolve_device(device)
+        self._dev = f"cuda:{self._device}"
+        self._table = torch.zeros(self._num_filters * (self._row_bytes // 4), dtype=torch.int32, device=self._dev)
+        self._els = torch.zeros(self._num_filters, dtype=torch.int64, device=self._dev)
+        self._cus = int(torch.cuda.get_device_properties(self._device).multi_processor_count)
+        self._add_policy = "auto"  # "auto" | "direct" | "grouped" (tests force each)
+        self._route = 0            # psk_bank_build's route: 0 auto per workgroup, 1 LDS image, 2 global atomics
+        self._last_path = None     # "direct" / "grouped": the way the last update took
+        self._split = None         # workgroups per filter; None: 1, or ceil(2 * CUs / num_filters) for a bank of fewer than 2 * CUs filters
+
+    # ------------------------------------------------------------------ properties
+    num_filters = property(lambda self: self._num_filters)
+    number_bits = property(lambda self: self._num_bits)
+    number_hashes = property(lambda self: self._number_hashes)
+    row_bytes = property(lambda self: self._row_bytes)
+    estimated_elements = property(lambda self: self._est_elements)
+    false_positive_rate = property(lambda self: self._fpr)
+    hash_function = property(lambda self: self._hash_func)
+    device = property(lambda self: self._device)
+
+    @property
+    def table_tensor(self):
+        """the int32 tensor [num_filters, row_bytes / 4] backing the bank (a view: writes through it are the caller's business)"""
+        return self._table.view(self._num_filters, self._row_bytes // 4)
+
+    @property
+    def elements_added(self) -> np.ndarray:
+        """int64 per filter: the number of keys sent there, repeats counted (bloom.py:239)"""
+        return self._els.cpu().numpy()
+
+    @property
+    def _stream(self):
+        if _raw_stream is not None:
+            return _raw_stream(self._device) or None
+        return torch.cuda.current_stream(self._device).cuda_stream or None
+
+    def synchronize(self) -> None:
+        torch.cuda.current_stream(self._device).synchronize()
+
+    def clear(self, f=None) -> None:
+        """empty filter ``f``, or every filter"""
+        if f is None:
+            self._table.zero_()
+            self._els.zero_()
+        else:
+            self.table_tensor[self._index(f)].zero_()
+            self._els[self._index(f)] = 0
+
+    def _index(self, f) -> int:
+        f = int(f)
+        if not 0 <= f < self._num_filters:
+            raise IndexError(f"filter {f} out of range [0, {self._num_filters})")
+        return f
+
+    # ------------------------------------------------------------------ batches, ids, offsets
+    def _batch(self, keys) -> KeyBatch:
+        if self._is_fused:
+            b = pack_keys(keys)
+        elif self._digest is not None:
+            b = digest_batch(keys, self._digest, self._number_hashes, self._device, self._stream)
+        else:
+            if isinstance(keys, (str, bytes, bytearray, memoryview)):
+                keys = [keys]
+            b = pack_hashes([self._hash_func(k, self._number_hashes) for k in keys], self._number_hashes) \
+                if len(keys) else pack_hashes(np.zeros((0, self._number_hashes), dtype=np.uint64), self._number_hashes)
+        return self._on_device(b)
+
+    def _on_device(self, b: KeyBatch) -> KeyBatch:
+        if b.where == N.DEVICE and b.device is not None and b.device != self._device:
+            raise ValueError(f"key batch lives on cuda:{b.device}, the bank on cuda:{self._device}")
+        return b
+
+    def _ids(self, ids, n: int, where: int, validate: bool):
+        """-> the ids where the keys are: an int64 numpy array (host keys) or an int64 tensor (device keys), checked"""
+        is_dev = torch is not None and isinstance(ids, torch.Tensor) and ids.is_cuda
+        if is_dev:
+            if ids.dim() != 1 or ids.is_floating_point() or ids.dtype == torch.bool:
+                raise TypeError("ids must be a 1-D integer tensor")
+            if ids.numel() != n:
+                raise ValueError("ids length differs from the number of keys")
+            if ids.device.index != self._device:
+                raise ValueError(f"ids live on cuda:{ids.device.index}, the bank on cuda:{self._device}")
+            if validate and n:  # one reduction, one synchronisation
+                lo, hi = torch.aminmax(ids)
+                if int(lo.item()) < 0 or int(hi.item()) >= self._num_filters:
+                    raise ValueError(f"filter ids must lie in [0, {self._num_filters})")
+            return ids.to(torch.int64) if where == N.DEVICE else ids.cpu().numpy().astype(np.int64)
+        a = ids.numpy() if torch is not None and isinstance(ids, torch.Tensor) else np.asarray(ids)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise TypeError("ids must be a 1-D integer array")
+        if a.size != n:
+            raise ValueError("ids length differs from the number of keys")
+        a = a.astype(np.int64, copy=False)
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= self._num_filters):  # host ids are always checked
+            raise ValueError(f"filter ids must lie in [0, {self._num_filters})")
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self._dev) if where == N.DEVICE else a
+
+    def _offsets(self, offs, n: int, where: int, validate: bool):
+        """filter_offsets[num_filters + 1] -> as _ids: where the keys are, checked (non-decreasing, from 0 to n)"""
+        is_dev = torch is not None and isinstance(offs, torch.Tensor) and offs.is_cuda
+        F = self._num_filters
+        if is_dev:
+            if offs.dim() != 1 or offs.numel() != F + 1 or offs.is_floating_point() or offs.dtype == torch.bool:
+                raise TypeError(f"filter_offsets must be {F + 1} integers")
+            if offs.device.index != self._device:
+                raise ValueError(f"filter_offsets live on cuda:{offs.device.index}, the bank on cuda:{self._device}")
+            o = offs.to(torch.int64).contiguous()
+            if validate:  # one reduction, one synchronisation
+                bad = (o[1:] < o[:-1]).any() | (o[0] != 0) | (o[-1] != n)
+                if bool(bad.item()):
+                    raise ValueError("filter_offsets must be non-decreasing, start at 0 and end at the number of keys")
+            return o if where == N.DEVICE else o.cpu().numpy()
+        a = offs.numpy() if torch is not None and isinstance(offs, torch.Tensor) else np.asarray(offs)
+        if a.ndim != 1 or a.size != F + 1 or a.dtype.kind not in "iu":
+            raise TypeError(f"filter_offsets must be {F + 1} integers")
+        a = np.ascontiguousarray(a.astype(np.int64, copy=False))
+        if (np.diff(a) < 0).any() or int(a[0]) != 0 or int(a[-1]) != n:
+            raise ValueError("filter_offsets must be non-decreasing, start at 0 and end at the number of keys")
+        return torch.from_numpy(a).to(self._dev) if where == N.DEVICE else a
+
+    @staticmethod
+    def _addr(x) -> int:
+        if isinstance(x, np.ndarray):
+            return x.ctypes.data if x.size else 0
+        return x.data_ptr() if x.numel() else 0
+
+    def _ids_u32(self, ids):
+        """int64 ids -> the uint32 words the engine reads (num_filters < 2^31: the low word)"""
+        if isinstance(ids, np.ndarray):
+            return np.ascontiguousarray(ids.astype(np.uint32))
+        return ids.to(torch.int32).contiguous()
+
+    def split_for(self) -> int:
+        """workgroups per filter of a grouped build: 1 unless the bank has fewer than twice as many filters as the device has CUs"""
+        if self._split is not None:
+            return int(self._split)
+        return 1 if self._num_filters >= 2 * self._cus else -(-2 * self._cus // self._num_filters)
+
+    def _grouped_pays(self, n: int) -> bool:
+        """the automatic choice for device keys with ids: sort + grouped build from BANK_GROUP_MIN_KEYS keys on, where a filter's mean share of
+        the batch is a segment that route 0 gives the LDS image (and the row fits it)"""
+        if BANK_GROUP_MIN_KEYS is None or n < BANK_GROUP_MIN_KEYS or self._row_bytes > BANK_LDS_ROW_BYTES:
+            return False
+        return n * self._number_hashes * BANK_ROUTE_R >= self._num_filters * (self._row_bytes // 4)
+
+    # ------------------------------------------------------------------ updates
+    def _add_direct(self, b: KeyBatch, ids) -> None:
+        self._last_path = "direct"
+        L = N.lib()
+        for lo in range(0, b.n, self._CHUNK):
+            hi = min(b.n, lo + self._CHUNK)
+            c, w = _slice_batch(b, lo, hi), self._ids_u32(ids[lo:hi])
+            N.check(L.psk_bank_add(self._table.data_ptr(), self._num_filters, self._num_bits, self._number_hashes, *c.args(), c.where,
+                                   self._addr(w) or None, self._device, self._stream))
+
+    def _build(self, b: KeyBatch, seg, perm) -> None:
+        """seg int64[F + 1] on the device (positions in perm, or in the batch when perm is None), perm int32[n] on the device or None"""
+        self._last_path = "grouped"
+        L = N.lib()
+        if b.n > self._CHUNK:
+            raise ValueError("a grouped call takes fewer than 2^32 keys")
+        N.check(L.psk_bank_build(self._table.data_ptr(), self._num_filters, self._num_bits, self._number_hashes, *b.args(), seg.data_ptr(),
+                                 perm.data_ptr() if perm is not None else None, self.split_for(), int(self._route), self._device, self._stream))
+
+    def _add_batch(self, b: KeyBatch, ids, filter_offsets, validate: bool) -> None:
+        if (ids is None) == (filter_offsets is None):
+            raise TypeError("pass either ids or filter_offsets")
+        if self._add_policy not in ("auto", "direct", "grouped"):
+            raise ValueError(f"unknown _add_policy {self._add_policy!r}")
+        F = self._num_filters
+        if filter_offsets is not None:
+            offs = self._offsets(filter_offsets, b.n, b.where, validate)
+            if b.n == 0:
+                return
+            if b.where == N.DEVICE and self._add_policy != "direct":  # keys that arrive grouped: the build kernel as they lie
+                self._build(b, offs, None)
+            elif b.where == N.DEVICE:
+                self._add_direct(b, torch.repeat_interleave(torch.arange(F, device=self._dev), offs[1:] - offs[:-1]))
+            else:  # host keys always go direct
+                self._add_direct(b, np.repeat(np.arange(F, dtype=np.int64), np.diff(offs)))
+            counts = offs[1:] - offs[:-1]
+            self._els += counts if b.where == N.DEVICE else torch.from_numpy(np.ascontiguousarray(counts)).to(self._dev)
+            return
+        idv = self._ids(ids, b.n, b.where, validate)
+        if b.n == 0:
+            return
+        grouped = b.where == N.DEVICE and b.n <= self._CHUNK and (
+            self._add_policy == "grouped" or (self._add_policy == "auto" and self._grouped_pays(b.n)))
+        if b.where == N.HOST:
+            self._add_direct(b, idv)
+            self._els += torch.from_numpy(np.bincount(idv, minlength=F).astype(np.int64)).to(self._dev)
+            return
+        if not validate:  # unchecked device ids: the engine skips ids >= num_filters, the counts must skip them too
+            counts = torch.bincount(torch.where((idv < 0) | (idv >= F), F, idv), minlength=F + 1)[:F]
+        else:
+            counts = torch.bincount(idv, minlength=F)
+        if grouped:
+            srt, perm = torch.sort(idv, stable=True)
+            seg = torch.searchsorted(srt, torch.arange(F + 1, device=self._dev, dtype=torch.int64))
+            self._build(b, seg.contiguous(), perm.to(torch.int32).contiguous())
+        else:
+            self._add_direct(b, idv)
+        self._els += counts
+
+    def add_many(self, keys, ids=None, filter_offsets=None, validate: bool = True) -> None:
+        """filter ``ids[i]`` gets key ``i`` -- or, for keys that are already grouped by filter, filter ``f`` gets keys
+        ``filter_offsets[f]:filter_offsets[f + 1]``.  An id outside the bank raises ``ValueError`` before anything is launched; device ids /
+        offsets are checked with one reduction and one synchronisation unless ``validate=False`` (then an id beyond the bank is skipped)."""
+        self._add_batch(self._batch(keys), ids, filter_offsets, validate)
+
+    def add_alt_many(self, hashes, ids=None, filter_offsets=None, validate: bool = True) -> None:
+        """:meth:`add_many` for pre-computed hashes: (n, >= k) uint64"""
+        self._add_batch(self._on_device(pack_hashes(hashes, self._number_hashes)), ids, filter_offsets, validate)
+
+    # ------------------------------------------------------------------ lookups
+    def _check_batch(self, b: KeyBatch, ids, validate: bool):
+        idv = self._ids(ids, b.n, b.where, validate)
+        L = N.lib()
+        if b.where == N.DEVICE:
+            out = torch.empty(b.n, dtype=torch.uint8, device=self._dev)
+        else:
+            out = np.empty(b.n, dtype=np.uint8)
+        for lo in range(0, b.n, self._CHUNK):  # (n = 0 launches nothing)
+            hi = min(b.n, lo + self._CHUNK)
+            c, w = _slice_batch(b, lo, hi), self._ids_u32(idv[lo:hi])
+            N.check(L.psk_bank_check(self._table.data_ptr(), self._num_filters, self._num_bits, self._number_hashes, *c.args(), c.where,
+                                     self._addr(w) or None, self._addr(out[lo:hi]) or None, self._device, self._stream))
+        return out.view(np.bool_) if isinstance(out, np.ndarray) else out.view(torch.bool)
+
+    def check_many(self, keys, ids, validate: bool = True):
+        """``key_i in filter ids[i]`` for every key: numpy bool[n] for host keys, torch.bool on the device for device keys"""
+        return self._check_batch(self._batch(keys), ids, validate)
+
+    def check_alt_many(self, hashes, ids, validate: bool = True):
+        return self._check_batch(self._on_device(pack_hashes(hashes, self._number_hashes)), ids, validate)
+
+    # ------------------------------------------------------------------ single filters
+    def filter(self, f) -> BloomFilter:
+        """a :class:`BloomFilter` COPY of filter ``f`` (table and ``elements_added``): export, union, estimate_elements ... all work on it"""
+        f = self._index(f)
+        blm = BloomFilter(self._est_elements, self._fpr, hash_function=self._hash_arg, device=self._device)
+        t = blm._tab
+        N.check(N.lib().psk_table_or(t.ptr, self.table_tensor[f].data_ptr(), t.nwords, t.device, t.stream))  # (blm starts empty)
+        blm.elements_added = int(self._els[f].item())
+        return blm
+
+    def set_filter(self, f, blm: BloomFilter) -> None:
+        """copy ``blm`` (table and ``elements_added``) into filter ``f``; a filter of another geometry or hash family raises"""
+        f = self._index(f)
+        if not isinstance(blm, BloomFilter) or type(blm)._KIND != "bloom":
+            raise TypeError("set_filter takes a BloomFilter")
+        if blm.number_bits != self._num_bits or blm.number_hashes != self._number_hashes or \
+                list(blm.hashes("test")) != list(self._hash_func("test", self._number_hashes)):
+            raise SimilarityError("the filter's geometry or hash function differs from the bank's")
+        if blm.device != self._device:
+            raise ValueError(f"the filter lives on cuda:{blm.device}, the bank on cuda:{self._device}")
+        blm._flush()
+        _ = blm._tab.ptr  # (the engine applies what it deferred before the tensor is read)
+        self.table_tensor[f].copy_(blm._tab.tensor)
+        self._els[f] = int(blm.elements_added)
+
+    def __str__(self) -> str:
+        return (f"BloomFilterBank:\n\tfilters: {self._num_filters}\n\tbits per filter: {self._num_bits}\n\tnumber hashes: {self._number_hashes}\n"
+                f"\trow bytes: {self._row_bytes}\n\telements added: {int(self._els.sum().item())}\n")
