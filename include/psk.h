@@ -430,6 +430,30 @@ int psk_bank_build(void *table_dev, uint64_t filters, uint64_t m_bits, uint32_t 
                    uint64_t n, uint32_t key_len, const uint64_t *seg_dev, const uint32_t *perm_dev, uint32_t split, int route, int device,
                    void *stream);
 
+/* The slice image: the bank transposed, for "which filters may hold this key" (the bit-sliced signatures of BIGSI / COBS).  All filters of a
+ * bank share m_bits, k and the hash family, so a key has the same k bit positions in every row; the filters that pass bloom.py:261-272 for
+ * the key are the AND of k rows of the transposed table.
+ *   layout  slices = uint32[m_bits][psk_bank_slice_row_bytes(filters) / 4] in device memory, owned by the caller, 16-byte aligned;
+ *           psk_bank_slice_row_bytes(filters) = ceil(filters / 8) rounded up to 16 (host only).  Bit f of slice row p (word f >> 5, bit f & 31,
+ *           LSB-first) == bit p of bank row f.  Columns at and beyond `filters` are zero in every row; a bank row's pad bits (p >= m_bits) have
+ *           no slice row.  Byte offsets are 64-bit: m_bits * slice_row_bytes may pass 2^32.
+ *   slices  STORES (not ORs) the word columns of filters [first_filter, last_filter) of every slice row from the table: a filter that was
+ *           cleared is cleared in the image.  first_filter is a multiple of 32; last_filter is a multiple of 32 or == filters, and then the
+ *           row's pad words behind the last filter are written (as zero) too.  Words outside the range are not touched; (0, filters) writes the
+ *           whole image.  An empty range does nothing; anything else is PSK_EINVAL.  Enqueue only.
+ *   match   for key i: bit f of mask_dev[i][..] (uint32[n][slice_row_bytes / 4], 16-byte aligned) is 1 exactly when all k bits of key i are set
+ *           in filter f -- what psk_bank_check answers for (i, f) -- and columns >= filters are 0; count_dev[i] = the number of set bits of that
+ *           row; ids_dev[out_offsets_dev[i] ...] = its set columns, ascending (out_offsets_dev = uint64[n], the exclusive prefix sums of a
+ *           counts call).  The outputs are device memory whatever `where` says; each may be NULL, at least one must be given, ids_dev and
+ *           out_offsets_dev go together.  Keys follow `where` (a PSK_HOST call returns when the kernel has read them).  k <= 64: the k
+ *           positions of a workgroup's 256 keys live in k * 1024 bytes of LDS.  n == 0 launches nothing. */
+uint64_t psk_bank_slice_row_bytes(uint64_t filters);
+int psk_bank_slices(const void *table_dev, uint64_t filters, uint64_t m_bits, void *slices_dev, uint64_t first_filter, uint64_t last_filter,
+                    int device, void *stream);
+int psk_bank_match(const void *slices_dev, uint64_t filters, uint64_t m_bits, uint32_t k, int layout, const void *data, const uint64_t *offsets,
+                   uint64_t n, uint32_t key_len, int where, uint32_t *mask_dev, uint32_t *count_dev, const uint64_t *out_offsets_dev,
+                   uint32_t *ids_dev, int device, void *stream);
+
 /* ------------------------------------------------------------ CuckooFilter
  * cuckoo/cuckoo.py: `capacity` buckets of `bucket_size` fingerprints of `fp_bits` bits.  No handle: the caller owns (device memory)
  *   buckets   uint32[capacity][bucket_size], every row filled from the left, its unused slots 0 (an export is this array plus the footer)

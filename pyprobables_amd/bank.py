@@ -7,6 +7,10 @@ one handle and one launch per filter.  Row ``f`` of :attr:`table_tensor` is that
 Two routes lead into the table (``include/psk.h``): *direct* -- every key carries a filter id, its k probes are atomics
 into that row (``psk_bank_add``) -- and *grouped* -- the keys of a filter lie (or are sorted) together, one workgroup sets a filter's bits in
 an LDS image of the row and ORs the image into the table once (``psk_bank_build``).
+
+"Which filters may hold this key?" is answered from a second copy of the table, the *slice image*: the bank transposed (``psk_bank_slices``),
+row ``p`` holding bit ``p`` of every filter.  All filters share the geometry and the hash family, so the answer for one key is the AND of
+its k slice rows (``psk_bank_match``).  The image is allocated on the first match and refreshed lazily: updates only mark it stale.
 """
 
 from __future__ import annotations
@@ -18,7 +22,7 @@ import numpy as np
 from . import _native as N
 from ._base import _raw_stream, _resolve_device
 from .bloom import BloomFilter
-from .exceptions import NativeLibraryError, SimilarityError
+from .exceptions import NativeLibraryError, NotSupportedError, SimilarityError
 from .hashes import default_fnv_1a, device_digest, is_fused_fnv
 from .keys import KeyBatch, digest_batch, pack_hashes, pack_keys
 
@@ -34,6 +38,8 @@ except Exception:  # pragma: no cover
 BANK_GROUP_MIN_KEYS = 1 << 21
 BANK_ROUTE_R = 16           # kBankRouteR of csrc/psk_bank.hip: route 0 takes the LDS image for a part with keys * k * R >= the row's words
 BANK_LDS_ROW_BYTES = 65536  # rows beyond it never take the LDS image
+BANK_MATCH_MAX_HASHES = 64  # psk_bank_match keeps a workgroup's k * 256 bit positions in LDS: 64 KiB at the cap
+BANK_SLICE_MAX_GROUPS = 8   # more stale 32-filter column groups than this: the next match transposes the whole bank, not group by group
 _ELEM = {N.KEYS_FIXED: 1, N.KEYS_VARLEN8: 1, N.KEYS_VARLEN32: 4, N.KEYS_HASHES: 8}
 
 
@@ -100,6 +106,11 @@ class BloomFilterBank:
         self._route = 0            # psk_bank_build's route: 0 auto per workgroup, 1 LDS image, 2 global atomics
         self._last_path = None     # "direct" / "grouped": the way the last update took
         self._split = None         # workgroups per filter; None: 1, or ceil(2 * CUs / num_filters) for a bank of fewer than 2 * CUs filters
+        self._slice_row_bytes = int(L.psk_bank_slice_row_bytes(self._num_filters))
+        self._slices = None        # the slice image (match_many), allocated on the first match
+        self._stale_all = True     # the image lags behind the table: everywhere / in these 32-filter column groups
+        self._stale_groups = set()
+        self._last_refresh = None  # the (first, last) filter spans of the last refresh (tests)
 
     # ------------------------------------------------------------------ properties
     num_filters = property(lambda self: self._num_filters)
@@ -135,9 +146,11 @@ class BloomFilterBank:
         if f is None:
             self._table.zero_()
             self._els.zero_()
+            self._mark_stale()
         else:
             self.table_tensor[self._index(f)].zero_()
             self._els[self._index(f)] = 0
+            self._mark_stale(self._index(f))
 
     def _index(self, f) -> int:
         f = int(f)
@@ -239,6 +252,7 @@ class BloomFilterBank:
     # ------------------------------------------------------------------ updates
     def _add_direct(self, b: KeyBatch, ids) -> None:
         self._last_path = "direct"
+        self._mark_stale()
         L = N.lib()
         for lo in range(0, b.n, self._CHUNK):
             hi = min(b.n, lo + self._CHUNK)
@@ -249,6 +263,7 @@ class BloomFilterBank:
     def _build(self, b: KeyBatch, seg, perm) -> None:
         """seg int64[F + 1] on the device (positions in perm, or in the batch when perm is None), perm int32[n] on the device or None"""
         self._last_path = "grouped"
+        self._mark_stale()
         L = N.lib()
         if b.n > self._CHUNK:
             raise ValueError("a grouped call takes fewer than 2^32 keys")
@@ -327,6 +342,102 @@ class BloomFilterBank:
     def check_alt_many(self, hashes, ids, validate: bool = True):
         return self._check_batch(self._on_device(pack_hashes(hashes, self._number_hashes)), ids, validate)
 
+    # ------------------------------------------------------------------ which filters may hold a key: the slice image
+    @property
+    def slice_row_bytes(self) -> int:
+        """bytes of one row of the slice image: ceil(num_filters / 8) rounded up to 16"""
+        return self._slice_row_bytes
+
+    @property
+    def slice_tensor(self):
+        """the int32 tensor [number_bits, slice_row_bytes / 4] of the slice image (row p holds bit p of every filter), or None before the
+        first match; it may be stale: :meth:`refresh_slices` brings it up to date"""
+        return None if self._slices is None else self._slices.view(self._num_bits, self._slice_row_bytes // 4)
+
+    def drop_slices(self) -> None:
+        """free the slice image; the next match builds it again"""
+        self._slices = None
+        self._mark_stale()
+
+    def invalidate_slices(self) -> None:
+        """for callers who wrote through :attr:`table_tensor`: the next match transposes the whole bank again"""
+        self._mark_stale()
+
+    def _mark_stale(self, f=None) -> None:
+        """a host flag, no launch: every column of the image (f is None) or the 32-filter column group of filter f is out of date"""
+        if f is None:
+            self._stale_all = True
+            self._stale_groups.clear()
+        elif not self._stale_all:
+            self._stale_groups.add(int(f) >> 5)
+            if len(self._stale_groups) > BANK_SLICE_MAX_GROUPS:
+                self._mark_stale()
+
+    def refresh_slices(self) -> None:
+        """bring the slice image up to date now (allocating it if need be): the whole bank, or one ranged transpose per stale column group"""
+        if self._slices is None:
+            self._slices = torch.zeros(self._num_bits * (self._slice_row_bytes // 4), dtype=torch.int32, device=self._dev)
+            self._stale_all = True
+        L, F = N.lib(), self._num_filters
+        spans = [(0, F)] if self._stale_all else [(32 * g, min(32 * g + 32, F)) for g in sorted(self._stale_groups)]
+        for lo, hi in spans:
+            N.check(L.psk_bank_slices(self._table.data_ptr(), F, self._num_bits, self._slices.data_ptr(), lo, hi, self._device, self._stream))
+        self._last_refresh = spans
+        self._stale_all = False
+        self._stale_groups.clear()
+
+    def _match_batch(self, b: KeyBatch, form: str):
+        if form not in ("mask", "count", "ids"):
+            raise ValueError(f"form must be 'mask', 'count' or 'ids', not {form!r}")
+        if self._number_hashes > BANK_MATCH_MAX_HASHES:
+            raise NotSupportedError(f"match_many takes filters of at most {BANK_MATCH_MAX_HASHES} hashes (this bank has {self._number_hashes}): "
+                                    "use check_many(keys, ids) with the filter ids spelled out")
+        if b.n > self._CHUNK:
+            raise ValueError("a match call takes fewer than 2^32 keys")
+        if self._stale_all or self._stale_groups or self._slices is None:
+            self.refresh_slices()
+        L, n, words = N.lib(), b.n, self._slice_row_bytes // 4
+        host = b.where == N.HOST
+
+        def call(mask=None, count=None, offs=None, ids=None):
+            if n:
+                N.check(L.psk_bank_match(self._slices.data_ptr(), self._num_filters, self._num_bits, self._number_hashes, *b.args(), b.where,
+                                         *(None if t is None else t.data_ptr() for t in (mask, count, offs, ids)), self._device, self._stream))
+
+        if form == "mask":
+            mask = torch.empty((n, words), dtype=torch.int32, device=self._dev)
+            call(mask=mask)
+            return mask.cpu().numpy().view(np.uint32) if host else mask
+        count = torch.empty(n, dtype=torch.int32, device=self._dev)
+        call(count=count)
+        if form == "count":
+            return count.cpu().numpy() if host else count
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=self._dev)
+        torch.cumsum(count, 0, out=offsets[1:])
+        ids = torch.empty(int(offsets[-1].item()), dtype=torch.int32, device=self._dev)
+        if ids.numel():
+            call(offs=offsets, ids=ids)
+        return (offsets.cpu().numpy(), ids.cpu().numpy()) if host else (offsets, ids)
+
+    def match_many(self, keys, form: str = "mask"):
+        """every filter that may hold each key (``key in filter f`` of bloom.py:261-272 for all f at once), read from the slice image.
+        ``form="mask"``: int32 [n, slice_row_bytes / 4], bit ``f & 31`` of word ``f >> 5`` of row i is set when filter f may hold key i;
+        ``"count"``: int32 [n], the number of such filters; ``"ids"``: ``(offsets int64[n + 1], ids int32[total])``, the filters of key i are
+        ``ids[offsets[i]:offsets[i + 1]]``, ascending.  Device keys give tensors on the device, host keys numpy arrays (the mask as uint32)."""
+        return self._match_batch(self._batch(keys), form)
+
+    def match_alt_many(self, hashes, form: str = "mask"):
+        """:meth:`match_many` for pre-computed hashes: (n, >= k) uint64"""
+        return self._match_batch(self._on_device(pack_hashes(hashes, self._number_hashes)), form)
+
+    def match(self, key) -> list:
+        """the ids of the filters that may hold ``key``, ascending"""
+        b = self._batch(key)
+        if b.n != 1:
+            raise TypeError("match takes one key; use match_many for a batch")
+        _, ids = self._match_batch(b, "ids")
+        return [int(f) for f in (ids if isinstance(ids, np.ndarray) else ids.cpu().numpy())]
+
     # ------------------------------------------------------------------ single filters
     def filter(self, f) -> BloomFilter:
         """a :class:`BloomFilter` COPY of filter ``f`` (table and ``elements_added``): export, union, estimate_elements ... all work on it"""
@@ -351,6 +462,7 @@ class BloomFilterBank:
         _ = blm._tab.ptr  # (the engine applies what it deferred before the tensor is read)
         self.table_tensor[f].copy_(blm._tab.tensor)
         self._els[f] = int(blm.elements_added)
+        self._mark_stale(f)
 
     def __str__(self) -> str:
         return (f"BloomFilterBank:\n\tfilters: {self._num_filters}\n\tbits per filter: {self._num_bits}\n\tnumber hashes: {self._number_hashes}\n"
