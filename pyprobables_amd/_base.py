@@ -1,19 +1,26 @@
-"""Device-side plumbing shared by the three sketches: one C-ABI handle + the HBM-resident table.
+"""Device-side plumbing of every structure in the package.
 
-The table lives in a torch tensor (so it can be handed to RCCL through ``torch.distributed`` without a
-copy) and is *borrowed* by the engine (``ext_table`` of ``psk_*_create``).  All work is enqueued on
-torch's current HIP stream for that device.
+All work is enqueued on torch's current HIP stream of the structure's device (`current_stream`), a structure without a device raises
+(`require_device`), a device key batch must live where the structure does (`same_device`), a batch call's result goes where its keys
+are (`result_buffer`, `as_bool`), and the runs of equal values in a batch come from one stable sort (`equal_groups`).
+:class:`DeviceResident` is the base of the structures that own their device tensors themselves (QuotientFilter, the cuckoo filters,
+BloomFilterBank); :class:`DeviceTable` is what the three sketches with a C-ABI handle hold: the handle + the HBM-resident table.  That
+table lives in a torch tensor (so it can be handed to RCCL through ``torch.distributed`` without a copy) and is *borrowed* by the
+engine (``ext_table`` of ``psk_*_create``).  None of this is on a single-key path (`OneKey`).
 """
 
 from __future__ import annotations
 
 import ctypes as C
+from typing import TYPE_CHECKING
 
 import numpy as np
 
 from . import _native as N
 from .exceptions import NativeLibraryError
-from .keys import KeyBatch
+
+if TYPE_CHECKING:  # (keys.py takes `result_buffer` from here)
+    from .keys import KeyBatch
 
 try:
     import torch
@@ -34,6 +41,77 @@ def _resolve_device(device) -> int:
 
 
 _raw_stream = getattr(getattr(torch, "_C", None), "_cuda_getCurrentRawStream", None) if torch is not None else None
+
+
+def current_stream(device: int):
+    """the raw handle of torch's CURRENT stream on `device`, looked up per call (callers switch streams); None: the default stream"""
+    if _raw_stream is not None:
+        return _raw_stream(device) or None
+    return torch.cuda.current_stream(device).cuda_stream or None
+
+
+def require_device(what: str, need_torch: bool = True) -> None:
+    """`what`: why the structure cannot do without a device, e.g. "the bank's table lives in GPU memory" """
+    N.lib()  # raises NativeLibraryError when the engine is missing
+    if N.device_count() == 0 or (need_torch and (torch is None or not torch.cuda.is_available())):
+        raise NativeLibraryError(f"no HIP device available: {what} and there is no CPU fallback")
+
+
+def same_device(b: KeyBatch, device: int, noun: str) -> KeyBatch:
+    if b.where == N.DEVICE and b.device is not None and b.device != device:
+        raise ValueError(f"key batch lives on cuda:{b.device}, the {noun} on cuda:{device}")
+    return b
+
+
+def result_buffer(where: int, n, np_dtype, torch_dtype, device: int):
+    """the result of a batch call goes where the batch lives: a torch tensor on `device` for device keys, a numpy array for host keys
+    (`n`: a length or a shape) -> (its address for the engine, None for an empty host result; finalize() -> the result)"""
+    if where == N.DEVICE:
+        t = torch.empty(n, dtype=torch_dtype, device=f"cuda:{device}")
+        return t.data_ptr(), (lambda: t)
+    a = np.empty(n, dtype=np_dtype)
+    # (the address from the array interface, not from `a.ctypes`: building that object is most of what this function costs)
+    return (a.__array_interface__["data"][0] if a.size else None), (lambda: a)
+
+
+def as_bool(res):
+    """the engine's uint8 flags as booleans, on either side (a view)"""
+    return res.view(np.bool_) if isinstance(res, np.ndarray) else res.view(torch.bool)
+
+
+def equal_groups(values):
+    """-> (order, first): the stable sort of `values` (``order.values``, ``order.indices``) and the mask of the sorted positions that
+    start a run of equal values"""
+    order = torch.sort(values, stable=True)
+    first = torch.ones(values.numel(), dtype=torch.bool, device=values.device)
+    first[1:] = order.values[1:] != order.values[:-1]
+    return order, first
+
+
+class DeviceResident:
+    """a structure that keeps its tables in torch tensors on ONE device.  A subclass sets ``_device`` (an index) and ``_NOUN`` (what
+    the messages call it) and writes none of the following itself."""
+
+    _NOUN = "structure"
+    _device = 0
+
+    @property
+    def device(self) -> int:
+        return self._device
+
+    @property
+    def _dev(self) -> str:
+        return f"cuda:{self._device}"
+
+    @property
+    def _stream(self):
+        return current_stream(self._device)
+
+    def _same_device(self, b: KeyBatch) -> KeyBatch:
+        return same_device(b, self._device, self._NOUN)
+
+    def synchronize(self) -> None:
+        torch.cuda.current_stream(self._device).synchronize()
 
 
 class OneKey:
@@ -61,10 +139,7 @@ class DeviceTable:
         self.device = _resolve_device(device)
         self.one = OneKey()
         self._cuda = torch is not None and torch.cuda.is_available()
-        if N.device_count() == 0:
-            raise NativeLibraryError(
-                "no HIP device available: the sketch table lives in GPU memory and there is no CPU fallback"
-            )
+        require_device("the sketch table lives in GPU memory", need_torch=False)
         if kind == "bloom":
             padded, create = L.psk_bloom_table_bytes(self.m), L.psk_bloom_create
             self.logical_bytes = (self.m + 7) // 8
@@ -104,9 +179,7 @@ class DeviceTable:
     @property
     def stream(self):
         if self._cuda:  # torch's CURRENT stream of the sketch's device, looked up per call (callers switch streams)
-            if _raw_stream is not None:
-                return _raw_stream(self.device) or None
-            return torch.cuda.current_stream(self.device).cuda_stream or None
+            return current_stream(self.device)
         return None
 
     def flush(self):
@@ -151,8 +224,7 @@ class DeviceTable:
         return self.padded_bytes // 4
 
     def check_batch(self, b: KeyBatch):
-        if b.where == N.DEVICE and b.device is not None and b.device != self.device:
-            raise ValueError(f"key batch lives on cuda:{b.device}, the sketch on cuda:{self.device}")
+        same_device(b, self.device, "sketch")
 
     def clear(self):
         N.check(N.lib().psk_clear(self.handle, self.stream))
@@ -205,11 +277,7 @@ class DeviceTable:
     # -- output buffers matching where the batch lives
     def out_buffer(self, b: KeyBatch, n_items: int, np_dtype, torch_dtype):
         """-> (address, finalize() -> result)"""
-        if b.where == N.DEVICE:
-            t = torch.empty(n_items, dtype=torch_dtype, device=f"cuda:{self.device}")
-            return t.data_ptr(), (lambda: t)
-        a = np.empty(n_items, dtype=np_dtype)
-        return (a.ctypes.data if a.size else 0), (lambda: a)
+        return result_buffer(b.where, n_items, np_dtype, torch_dtype, self.device)
 
 
 def weights_arg(w, n: int, np_dtype, where: int, keep: list, lo: int, hi: int, device: int | None = None):

@@ -20,11 +20,11 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
-from ._base import _raw_stream, _resolve_device
+from ._base import DeviceResident, _resolve_device, as_bool, require_device, result_buffer
 from .bloom import BloomFilter
-from .exceptions import NativeLibraryError, NotSupportedError, SimilarityError
+from .exceptions import NotSupportedError, SimilarityError
 from .hashes import default_fnv_1a, device_digest, is_fused_fnv
-from .keys import KeyBatch, digest_batch, pack_hashes, pack_keys
+from .keys import KeyBatch, hashed_batch, pack_hashes
 
 try:
     import torch
@@ -72,7 +72,7 @@ def _slice_batch(b: KeyBatch, lo: int, hi: int) -> KeyBatch:
     return KeyBatch(b.layout, b.data + int(offs[lo]) * _ELEM[b.layout], o.ctypes.data, hi - lo, 0, b.where, b.device, [*b.keep, o])
 
 
-class BloomFilterBank:
+class BloomFilterBank(DeviceResident):
     """``num_filters`` Bloom filters sized by ``(est_elements, false_positive_rate)`` as the reference sizes one (bloom.py:463-502).
 
     Keys are accepted as everywhere in the package (lists of ``str`` / ``bytes``, ``(n, L)`` uint8 arrays or tensors, ragged
@@ -80,6 +80,7 @@ class BloomFilterBank:
     evaluated on the host (the digest families on the device) and travels as pre-computed hashes, as in :class:`BloomFilter`."""
 
     _CHUNK = 2**32 - 1  # keys per engine call
+    _NOUN = "bank"
 
     def __init__(self, num_filters, est_elements, false_positive_rate, hash_function=None, device=None):
         if not (isinstance(num_filters, (int, np.integer)) and 0 < int(num_filters) < 2**31):
@@ -95,10 +96,8 @@ class BloomFilterBank:
         self._is_fused = is_fused_fnv(hash_function)
         self._digest = device_digest(self._hash_func)
         self._row_bytes = int(L.psk_bank_row_bytes(self._num_bits))
-        if N.device_count() == 0 or torch is None or not torch.cuda.is_available():
-            raise NativeLibraryError("no HIP device available: the bank's table lives in GPU memory and there is no CPU fallback")
+        require_device("the bank's table lives in GPU memory")
         self._device = _resolve_device(device)
-        self._dev = f"cuda:{self._device}"
         self._table = torch.zeros(self._num_filters * (self._row_bytes // 4), dtype=torch.int32, device=self._dev)
         self._els = torch.zeros(self._num_filters, dtype=torch.int64, device=self._dev)
         self._cus = int(torch.cuda.get_device_properties(self._device).multi_processor_count)
@@ -120,7 +119,6 @@ class BloomFilterBank:
     estimated_elements = property(lambda self: self._est_elements)
     false_positive_rate = property(lambda self: self._fpr)
     hash_function = property(lambda self: self._hash_func)
-    device = property(lambda self: self._device)
 
     @property
     def table_tensor(self):
@@ -131,15 +129,6 @@ class BloomFilterBank:
     def elements_added(self) -> np.ndarray:
         """int64 per filter: the number of keys sent there, repeats counted (bloom.py:239)"""
         return self._els.cpu().numpy()
-
-    @property
-    def _stream(self):
-        if _raw_stream is not None:
-            return _raw_stream(self._device) or None
-        return torch.cuda.current_stream(self._device).cuda_stream or None
-
-    def synchronize(self) -> None:
-        torch.cuda.current_stream(self._device).synchronize()
 
     def clear(self, f=None) -> None:
         """empty filter ``f``, or every filter"""
@@ -160,21 +149,7 @@ class BloomFilterBank:
 
     # ------------------------------------------------------------------ batches, ids, offsets
     def _batch(self, keys) -> KeyBatch:
-        if self._is_fused:
-            b = pack_keys(keys)
-        elif self._digest is not None:
-            b = digest_batch(keys, self._digest, self._number_hashes, self._device, self._stream)
-        else:
-            if isinstance(keys, (str, bytes, bytearray, memoryview)):
-                keys = [keys]
-            b = pack_hashes([self._hash_func(k, self._number_hashes) for k in keys], self._number_hashes) \
-                if len(keys) else pack_hashes(np.zeros((0, self._number_hashes), dtype=np.uint64), self._number_hashes)
-        return self._on_device(b)
-
-    def _on_device(self, b: KeyBatch) -> KeyBatch:
-        if b.where == N.DEVICE and b.device is not None and b.device != self._device:
-            raise ValueError(f"key batch lives on cuda:{b.device}, the bank on cuda:{self._device}")
-        return b
+        return self._same_device(hashed_batch(keys, self._hash_func, self._is_fused, self._digest, self._number_hashes, self._device, self._stream))
 
     def _ids(self, ids, n: int, where: int, validate: bool):
         """-> the ids where the keys are: an int64 numpy array (host keys) or an int64 tensor (device keys), checked"""
@@ -318,29 +293,26 @@ class BloomFilterBank:
 
     def add_alt_many(self, hashes, ids=None, filter_offsets=None, validate: bool = True) -> None:
         """:meth:`add_many` for pre-computed hashes: (n, >= k) uint64"""
-        self._add_batch(self._on_device(pack_hashes(hashes, self._number_hashes)), ids, filter_offsets, validate)
+        self._add_batch(self._same_device(pack_hashes(hashes, self._number_hashes)), ids, filter_offsets, validate)
 
     # ------------------------------------------------------------------ lookups
     def _check_batch(self, b: KeyBatch, ids, validate: bool):
         idv = self._ids(ids, b.n, b.where, validate)
         L = N.lib()
-        if b.where == N.DEVICE:
-            out = torch.empty(b.n, dtype=torch.uint8, device=self._dev)
-        else:
-            out = np.empty(b.n, dtype=np.uint8)
+        out = result_buffer(b.where, b.n, np.uint8, torch.uint8, self._device)[1]()
         for lo in range(0, b.n, self._CHUNK):  # (n = 0 launches nothing)
             hi = min(b.n, lo + self._CHUNK)
             c, w = _slice_batch(b, lo, hi), self._ids_u32(idv[lo:hi])
             N.check(L.psk_bank_check(self._table.data_ptr(), self._num_filters, self._num_bits, self._number_hashes, *c.args(), c.where,
                                      self._addr(w) or None, self._addr(out[lo:hi]) or None, self._device, self._stream))
-        return out.view(np.bool_) if isinstance(out, np.ndarray) else out.view(torch.bool)
+        return as_bool(out)
 
     def check_many(self, keys, ids, validate: bool = True):
         """``key_i in filter ids[i]`` for every key: numpy bool[n] for host keys, torch.bool on the device for device keys"""
         return self._check_batch(self._batch(keys), ids, validate)
 
     def check_alt_many(self, hashes, ids, validate: bool = True):
-        return self._check_batch(self._on_device(pack_hashes(hashes, self._number_hashes)), ids, validate)
+        return self._check_batch(self._same_device(pack_hashes(hashes, self._number_hashes)), ids, validate)
 
     # ------------------------------------------------------------------ which filters may hold a key: the slice image
     @property
@@ -428,7 +400,7 @@ class BloomFilterBank:
 
     def match_alt_many(self, hashes, form: str = "mask"):
         """:meth:`match_many` for pre-computed hashes: (n, >= k) uint64"""
-        return self._match_batch(self._on_device(pack_hashes(hashes, self._number_hashes)), form)
+        return self._match_batch(self._same_device(pack_hashes(hashes, self._number_hashes)), form)
 
     def match(self, key) -> list:
         """the ids of the filters that may hold ``key``, ascending"""

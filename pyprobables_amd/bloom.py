@@ -21,10 +21,10 @@ from textwrap import wrap
 import numpy as np
 
 from . import _native as N
-from ._base import DeviceTable
+from ._base import DeviceTable, as_bool
 from .exceptions import InitializationError, SimilarityError
 from .hashes import HashFuncT, HashResultsT, KeyT, default_fnv_1a, device_digest, is_fused_fnv
-from .keys import KeyBatch, digest_batch, one_key_bytes, pack_hashes, pack_keys
+from .keys import KeyBatch, hashed_batch, one_key_bytes, pack_hashes
 
 _LN2_SQUARED = 0.4804530139182   # bloom.py:477 (the literal the reference and its C sibling use)
 _LN2 = 0.6931471805599453        # bloom.py:478
@@ -218,15 +218,7 @@ class BloomFilter:
 
     def _batch(self, keys) -> KeyBatch:
         """keys -> device-ready batch; a custom hash_function is evaluated here, on the host, per key"""
-        if self._fused:
-            b = pack_keys(keys)
-        elif self._digest is not None:  # default_md5 / default_sha256: digest chains on the GPU
-            b = digest_batch(keys, self._digest, self._number_hashes, self._tab.device, self._tab.stream)
-        else:
-            if isinstance(keys, (str, bytes, bytearray, memoryview)):
-                keys = [keys]
-            b = pack_hashes([self._hash_func(k, self._number_hashes) for k in keys], self._number_hashes) \
-                if len(keys) else pack_hashes(np.zeros((0, self._number_hashes), dtype=np.uint64), self._number_hashes)
+        b = hashed_batch(keys, self._hash_func, self._is_fused, self._digest, self._number_hashes, self._tab.device, self._tab.stream)
         self._tab.check_batch(b)
         return b
 
@@ -238,8 +230,7 @@ class BloomFilter:
         self._flush()
         addr, fin = self._tab.out_buffer(b, b.n, np.uint8, _torch_dtype("uint8"))
         N.check(N.lib().psk_bloom_check(self._tab.handle, *b.args(), b.where, addr, self._tab.stream))
-        res = fin()
-        return res.view(np.bool_) if isinstance(res, np.ndarray) else res.view(_torch_dtype("bool"))
+        return as_bool(fin())
 
     def add(self, key: KeyT) -> None:
         """bloom.py:234-239; write-combined on the host (see ``_flush``)"""
@@ -296,8 +287,7 @@ class BloomFilter:
             new_addr, new = self._tab.out_buffer(b, 1, np.uint64, _torch_dtype("int64"))
         N.check(N.lib().psk_bloom_add_running(self._tab.handle, *b.args(), b.where, 0, addr, new_addr, self._tab.stream))
         self._els_added += b.n if count_seen else int(new()[0])
-        res = fin()
-        return res.view(np.bool_) if isinstance(res, np.ndarray) else res.view(_torch_dtype("bool"))
+        return as_bool(fin())
 
     def add_many_ordered(self, keys, count_seen: bool = True):
         """the loop ``seen = key in blm; blm.add(key)`` over a whole batch, exact: entry ``i`` of the result is what ``key_i in blm``
@@ -335,9 +325,9 @@ class BloomFilter:
         if kind == "late":
             return self._check_batch(b)
         self._flush()  # add() calls made since begin: the answer is against the table as it is NOW
-        out = torch_mod().empty(b.n, dtype=_torch_dtype("uint8"), device=f"cuda:{self._tab.device}")
-        N.check(N.lib().psk_bloom_check_finish(self._tab.handle, out.data_ptr(), self._tab.stream))
-        return out.view(_torch_dtype("bool"))
+        addr, fin = self._tab.out_buffer(b, b.n, np.uint8, _torch_dtype("uint8"))  # (a device batch)
+        N.check(N.lib().psk_bloom_check_finish(self._tab.handle, addr, self._tab.stream))
+        return as_bool(fin())
 
     def add_alt_many(self, hashes) -> None:
         """pre-hashed batch: (n, >=k) uint64"""
@@ -511,12 +501,6 @@ class BloomFilter:
         if cu == 0:
             return 1.0
         return self._combine(second, "psk_table_and")._cnt_number_bits_set() / cu
-
-
-def torch_mod():
-    import torch  # noqa: PLC0415
-
-    return torch
 
 
 def _torch_dtype(name: str):

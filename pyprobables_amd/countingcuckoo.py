@@ -24,6 +24,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _native as N
+from ._base import equal_groups
 from .cuckoo import _FOOTER, _NONE, CuckooFilter
 from . import cuckoo as _ck
 from .exceptions import InitializationError, NativeLibraryError, NotSupportedError
@@ -90,8 +91,8 @@ class CountingCuckooFilter(CuckooFilter):
 
     # ------------------------------------------------------------------ the table
     def _new_table(self) -> None:
-        self._buckets = torch.zeros((self._capacity, self._bucket_size, 2), dtype=torch.int32, device=self._dev())
-        self._fill = torch.zeros(self._capacity, dtype=torch.int32, device=self._dev())
+        self._buckets = torch.zeros((self._capacity, self._bucket_size, 2), dtype=torch.int32, device=self._dev)
+        self._fill = torch.zeros(self._capacity, dtype=torch.int32, device=self._dev)
         self._marks = None
 
     @property
@@ -170,8 +171,8 @@ class CountingCuckooFilter(CuckooFilter):
         u = int(fps.numel())
         tr = self._triples_of_fingerprints(fps)
         weights = mult.to(torch.int32)  # (a batch holds fewer than 2^32 keys; the bit pattern is the uint32)
-        missed = torch.empty(u, dtype=torch.uint8, device=self._dev())
-        flags = torch.empty(2, dtype=torch.int32, device=self._dev())
+        missed = torch.empty(u, dtype=torch.uint8, device=self._dev)
+        flags = torch.empty(2, dtype=torch.int32, device=self._dev)
         N.check(N.lib().psk_cck_add_counts(*self._geom(), *self._table(), tr.data_ptr(), weights.data_ptr(), u, missed.data_ptr(), flags.data_ptr(), self._device,
                                            self._stream))
         self._elements_added += k
@@ -199,10 +200,10 @@ class CountingCuckooFilter(CuckooFilter):
         that is placed directly keeps"""
         self._alloc()
         B = self._bucket_size
-        live = torch.arange(B, dtype=torch.int32, device=self._dev())[None, :] < self._fill[:, None]
+        live = torch.arange(B, dtype=torch.int32, device=self._dev)[None, :] < self._fill[:, None]
         bins = self._buckets[live]  # (k, 2)
         if leftover is not None:
-            first = torch.tensor([[v if v < 2**31 else v - 2**32 for v in leftover]], dtype=torch.int32, device=self._dev())
+            first = torch.tensor([[v if v < 2**31 else v - 2**32 for v in leftover]], dtype=torch.int32, device=self._dev)
             bins = torch.cat([first, bins])
         capacity = self._capacity * self._expansion_rate
         if not isinstance(capacity, int) or capacity < 1 or capacity >= 2**31:
@@ -239,17 +240,7 @@ class CountingCuckooFilter(CuckooFilter):
 
     def check_many(self, keys):
         """the count per key: numpy uint32 for host keys, an int32 (bit pattern of the uint32) torch tensor for device keys"""
-        self._alloc()
-        b = self._as_batch(keys)
-        self._check_batch(b)
-        args = (*self._geom(), self._fingerprint_size, *self._table(), *b.args())
-        if b.where == N.DEVICE:
-            out = torch.empty(b.n, dtype=torch.int32, device=self._dev())
-            N.check(N.lib().psk_cck_check(*args, N.DEVICE, out.data_ptr(), self._device, self._stream))
-            return out
-        out = np.empty(b.n, dtype=np.uint32)
-        N.check(N.lib().psk_cck_check(*args, N.HOST, out.ctypes.data if b.n else None, self._device, self._stream))
-        return out
+        return self._lookup(N.lib().psk_cck_check, keys, np.uint32, torch.int32)
 
     def check(self, key: KeyT) -> int:
         """The number of times an element was inserted (countingcuckoo.py:175-191)"""
@@ -261,23 +252,21 @@ class CountingCuckooFilter(CuckooFilter):
         on_device = b.where == N.DEVICE
         tr = self._triples(b)
         n = int(tr.shape[1])
-        out = torch.zeros(n, dtype=torch.bool, device=self._dev())
+        out = torch.zeros(n, dtype=torch.bool, device=self._dev)
         if n:
             # the requests of one fingerprint stand together in a stable sort: rank = position inside the group, group = its number
-            order = torch.sort(tr[0], stable=True)
+            order, first = equal_groups(tr[0])
             idx = torch.arange(n, dtype=torch.int64, device=tr.device)
-            first = torch.ones(n, dtype=torch.bool, device=tr.device)
-            first[1:] = order.values[1:] != order.values[:-1]
             starts = torch.nonzero(first).reshape(-1)
             group = torch.cumsum(first.to(torch.int64), 0) - 1
             rank = idx - starts[group]
             u = int(starts.numel())
             requests = torch.diff(starts, append=torch.tensor([n], dtype=torch.int64, device=tr.device)).to(torch.int32)
             distinct = tr[:, order.indices[starts]].contiguous()
-            granted = torch.empty(u, dtype=torch.int32, device=self._dev())
-            emptied = torch.empty(1, dtype=torch.int32, device=self._dev())
+            granted = torch.empty(u, dtype=torch.int32, device=self._dev)
+            emptied = torch.empty(1, dtype=torch.int32, device=self._dev)
             if self._marks is None:
-                self._marks = torch.zeros(self._capacity, dtype=torch.int32, device=self._dev())
+                self._marks = torch.zeros(self._capacity, dtype=torch.int32, device=self._dev)
             N.check(N.lib().psk_cck_remove(*self._geom(), *self._table(), distinct.data_ptr(), requests.data_ptr(), u, self._marks.data_ptr(), granted.data_ptr(),
                                            emptied.data_ptr(), self._device, self._stream))
             got = granted.to(torch.int64) & _NONE

@@ -14,7 +14,6 @@ their ``add_many`` is ``add_many_ordered`` plus the dict rule, written as the tw
 
 from __future__ import annotations
 
-import ctypes as C
 import math
 import struct
 from io import BytesIO, IOBase
@@ -29,7 +28,7 @@ from ._base import DeviceTable, weights_arg
 from .bloom import _existing_file, _torch_dtype
 from .exceptions import CountMinSketchError, InitializationError, NotSupportedError
 from .hashes import HashFuncT, HashResultsT, KeyT, default_fnv_1a, device_digest, is_fused_fnv
-from .keys import KeyBatch, digest_batch, one_key_bytes, pack_hashes, pack_keys
+from .keys import KeyBatch, hashed_batch, one_key_bytes, pack_hashes
 
 _I32_MAX, _I32_MIN = 2**31 - 1, -(2**31)
 _I64_MAX, _I64_MIN = 2**63 - 1, -(2**63)
@@ -219,15 +218,7 @@ class CountMinSketch:
 
     # ------------------------------------------------------------------ batches
     def _batch(self, keys) -> KeyBatch:
-        if self._fused:
-            b = pack_keys(keys)
-        elif self._digest is not None:  # default_md5 / default_sha256: digest chains on the GPU
-            b = digest_batch(keys, self._digest, self._depth, self._tab.device, self._tab.stream)
-        else:
-            if isinstance(keys, (str, bytes, bytearray, memoryview)):
-                keys = [keys]
-            b = pack_hashes([self._hash_function(k, self._depth) for k in keys], self._depth) if len(keys) \
-                else pack_hashes(np.zeros((0, self._depth), dtype=np.uint64), self._depth)
+        b = hashed_batch(keys, self._hash_function, self._is_fused, self._digest, self._depth, self._tab.device, self._tab.stream)
         self._tab.check_batch(b)
         return b
 
@@ -334,17 +325,9 @@ class CountMinSketch:
         w_addr, _ = weights_arg(w, b.n, np.int32, b.where, keep, lo, _I32_MAX, self._tab.device)
         wide = self._query == "mean-min"
         addr, fin = self._tab.out_buffer(b, b.n, np.int64 if wide else np.int32, _torch_dtype("int64" if wide else "int32"))
-        els_in = self.elements_added
-        if b.where == N.DEVICE:
-            import torch  # noqa: PLC0415
-
-            els = torch.empty(1, dtype=torch.int64, device=f"cuda:{self._tab.device}")
-            els_addr = els.data_ptr()
-        else:
-            els = C.c_int64(0)
-            els_addr = C.addressof(els)
-        N.check(fn(self._tab.handle, *b.args(), w_addr, b.where, _QUERIES[self._query], els_in, addr or None, els_addr, self._tab.stream))
-        self._els_added = int(els.item()) if b.where == N.DEVICE else els.value
+        els_addr, els = self._tab.out_buffer(b, 1, np.int64, _torch_dtype("int64"))  # elements_added behind the batch (read back for a device batch)
+        N.check(fn(self._tab.handle, *b.args(), w_addr, b.where, _QUERIES[self._query], self.elements_added, addr, els_addr, self._tab.stream))
+        self._els_added = int(els()[0])
         return fin()
 
     @staticmethod

@@ -131,28 +131,17 @@ __global__ __launch_bounds__(kBlock) void k_bank_build(Src src, uint32_t *tab, u
     }
 }
 
-Mod bank_mod(uint64_t m, bool *pow2)
+int slice_check_geometry(uint64_t filters, uint64_t m_bits)
 {
-    Mod md;
-    md.m = m;
-    *pow2 = (m & (m - 1)) == 0;
-    md.mask = m - 1;
-    md.magic = *pow2 ? 0 : (uint64_t)((((unsigned __int128)1) << 64) / m);
-    return md;
-}
-
-template <class F>
-int bank_with_pow2(bool pow2, F &&f)
-{
-    if (pow2) return f(std::true_type{});
-    return f(std::false_type{});
+    if (filters == 0 || filters > (1ULL << 32)) return fail(PSK_EINVAL, "a bank holds 1 .. 2^32 filters; %llu were asked for", (unsigned long long)filters);
+    if (m_bits == 0 || m_bits > kBankMaxBits) return fail(PSK_EINVAL, "a bank's filters hold 1 .. 2^31 bits; %llu were asked for", (unsigned long long)m_bits);
+    return PSK_OK;
 }
 
 int bank_check_args(const void *table_dev, uint64_t filters, uint64_t m_bits, uint32_t k, int layout, uint64_t n, uint32_t key_len)
 {
     if (!table_dev) return fail(PSK_EINVAL, "NULL table pointer");
-    if (filters == 0 || filters > (1ULL << 32)) return fail(PSK_EINVAL, "a bank holds 1 .. 2^32 filters; %llu were asked for", (unsigned long long)filters);
-    if (m_bits == 0 || m_bits > kBankMaxBits) return fail(PSK_EINVAL, "a bank's filters hold 1 .. 2^31 bits; %llu were asked for", (unsigned long long)m_bits);
+    PSK_TRY(slice_check_geometry(filters, m_bits));
     if (k == 0) return fail(PSK_EINVAL, "number of hashes must be > 0");
     if (n >> 32) return fail(PSK_EINVAL, "a bank call takes fewer than 2^32 keys; %llu were passed", (unsigned long long)n);
     if (layout == PSK_KEYS_HASHES && key_len < k) return fail(PSK_EINVAL, "pre-hashed batch carries %u hashes per key, the bank needs %u", key_len, k);
@@ -323,13 +312,6 @@ __global__ __launch_bounds__(kBlock) void k_bank_match(Src src, const uint4 *sli
     }
 }
 
-int slice_check_geometry(uint64_t filters, uint64_t m_bits)
-{
-    if (filters == 0 || filters > (1ULL << 32)) return fail(PSK_EINVAL, "a bank holds 1 .. 2^32 filters; %llu were asked for", (unsigned long long)filters);
-    if (m_bits == 0 || m_bits > kBankMaxBits) return fail(PSK_EINVAL, "a bank's filters hold 1 .. 2^31 bits; %llu were asked for", (unsigned long long)m_bits);
-    return PSK_OK;
-}
-
 }  // namespace
 
 extern "C" uint64_t psk_bank_row_bytes(uint64_t m_bits) { return psk_bloom_table_bytes(m_bits); }
@@ -340,10 +322,10 @@ extern "C" int psk_bank_add(void *table_dev, uint64_t filters, uint64_t m_bits, 
     PSK_TRY(bank_check_args(table_dev, filters, m_bits, k, layout, n, key_len));
     if (n && !ids) return fail(PSK_EINVAL, "ids is NULL");
     bool pow2;
-    const Mod md = bank_mod(m_bits, &pow2);
+    const Mod md = make_mod(m_bits, &pow2);
     const uint64_t row_words = psk_bank_row_bytes(m_bits) / 4;
     return bank_keyed_call(layout, data, offsets, n, key_len, where, ids, nullptr, 0, device, stream, [&](auto src, const uint32_t *ids_dev, void *, hipStream_t st) {
-        return bank_with_pow2(pow2, [&](auto P) { return launch_apply(src, BankAdd<P.value>{(uint32_t *)table_dev, row_words, filters, ids_dev, md, k}, n, st); });
+        return with_pow2(pow2, [&](auto P) { return launch_apply(src, BankAdd<P.value>{(uint32_t *)table_dev, row_words, filters, ids_dev, md, k}, n, st); });
     });
 }
 
@@ -353,10 +335,10 @@ extern "C" int psk_bank_check(const void *table_dev, uint64_t filters, uint64_t 
     PSK_TRY(bank_check_args(table_dev, filters, m_bits, k, layout, n, key_len));
     if (n && (!ids || !out)) return fail(PSK_EINVAL, "ids or out is NULL");
     bool pow2;
-    const Mod md = bank_mod(m_bits, &pow2);
+    const Mod md = make_mod(m_bits, &pow2);
     const uint64_t row_words = psk_bank_row_bytes(m_bits) / 4;
     return bank_keyed_call(layout, data, offsets, n, key_len, where, ids, out, n, device, stream, [&](auto src, const uint32_t *ids_dev, void *out_dev, hipStream_t st) {
-        return bank_with_pow2(pow2, [&](auto P) {
+        return with_pow2(pow2, [&](auto P) {
             return launch_apply(src, BankCheck<P.value>{(const uint32_t *)table_dev, row_words, filters, ids_dev, md, k, (uint8_t *)out_dev}, n, st);
         });
     });
@@ -380,11 +362,11 @@ extern "C" int psk_bank_build(void *table_dev, uint64_t filters, uint64_t m_bits
     PSK_TRY(stage_batch(ts.keys, ts.offs, layout, data, offsets, n, key_len, PSK_DEVICE, st, &b));
     if (n == 0) return PSK_OK;
     bool pow2;
-    const Mod md = bank_mod(m_bits, &pow2);
+    const Mod md = make_mod(m_bits, &pow2);
     const size_t lds = route != 2 && row_bytes <= kBankLdsRowBytes ? (size_t)row_bytes : 0;
     const dim3 grid((unsigned)(filters < kBankGridCap ? filters : kBankGridCap), split);
     return with_source(b, [&](auto src) {
-        return bank_with_pow2(pow2, [&](auto P) {
+        return with_pow2(pow2, [&](auto P) {
             hipLaunchKernelGGL((k_bank_build<decltype(src), P.value>), grid, dim3(kBlock), lds, st, src, (uint32_t *)table_dev, filters, (uint32_t)(row_bytes / 4), md, k, n,
                                seg_dev, perm_dev, route);
             HIP_TRY(hipGetLastError());
@@ -436,7 +418,7 @@ extern "C" int psk_bank_match(const void *slices_dev, uint64_t filters, uint64_t
     uint32_t lgG = 0;
     while (lgG < 6 && (1ULL << lgG) < quads) ++lgG;
     bool pow2;
-    const Mod md = bank_mod(m_bits, &pow2);
+    const Mod md = make_mod(m_bits, &pow2);
     PSK_USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     ThreadStage &ts = thread_stage();
@@ -444,7 +426,7 @@ extern "C" int psk_bank_match(const void *slices_dev, uint64_t filters, uint64_t
     PSK_TRY(stage_batch(ts.keys, ts.offs, layout, data, offsets, n, key_len, where, st, &b));
     if (n)
         PSK_TRY(with_source(b, [&](auto src) {
-            return bank_with_pow2(pow2, [&](auto P) {
+            return with_pow2(pow2, [&](auto P) {
                 hipLaunchKernelGGL((k_bank_match<decltype(src), P.value>), dim3(grid_for_keys(n)), dim3(kBlock), (size_t)k * kBlock * 4, st, src, (const uint4 *)slices_dev,
                                    (uint32_t)quads, md, k, n, lgG, (uint4 *)mask_dev, count_dev, out_offsets_dev, ids_dev);
                 HIP_TRY(hipGetLastError());

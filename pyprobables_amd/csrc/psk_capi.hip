@@ -1,7 +1,7 @@
 // psk_capi.hip -- the extern "C" boundary (include/psk.h), the part every sketch shares: errors, handle lifetime, the option table, clear,
 // table I/O, counters and scratch accounting.  The entry points that take keys live with their sketch (psk_bloom.hip, psk_cbf.hip,
 // psk_cms.hip, psk_hash.hip, psk_quotient.hip, psk_cuckoo.hip) over the staging layer of psk_stage.hpp; table algebra: psk_table_ops.hip.
-#include "psk_host.hpp"
+#include "psk_stage.hpp"
 
 #include <map>
 #include <mutex>
@@ -40,16 +40,6 @@ static uint64_t round16(uint64_t b) { return (b + 15) & ~15ULL; }
 extern "C" uint64_t psk_bloom_table_bytes(uint64_t m_bits) { return round16((m_bits + 7) / 8); }
 extern "C" uint64_t psk_cbf_table_bytes(uint64_t m) { return round16(4 * m); }
 extern "C" uint64_t psk_cms_table_bytes(uint64_t width, uint32_t depth) { return round16(4 * width * (uint64_t)depth); }
-
-static Mod make_mod(uint64_t m, bool *pow2)
-{
-    Mod md;
-    md.m = m;
-    *pow2 = (m & (m - 1)) == 0;
-    md.mask = m - 1;
-    md.magic = *pow2 ? 0 : (uint64_t)((((unsigned __int128)1) << 64) / m);
-    return md;
-}
 
 int ensure(DevBuf &b, uint64_t bytes)
 {

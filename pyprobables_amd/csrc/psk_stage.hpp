@@ -66,13 +66,29 @@ static int launch_apply(const Src &src, const Op &op, uint64_t n, hipStream_t st
     return PSK_OK;
 }
 
+// The modulus of a table of m cells: mask for a power of two (*pow2), else the Barrett magic floor(2^64 / m).
+static inline Mod make_mod(uint64_t m, bool *pow2)
+{
+    Mod md;
+    md.m = m;
+    *pow2 = (m & (m - 1)) == 0;
+    md.mask = m - 1;
+    md.magic = *pow2 ? 0 : (uint64_t)((((unsigned __int128)1) << 64) / m);
+    return md;
+}
+
 // Dispatch a functor over the table's modulus as a compile-time constant: f(std::true_type{}) for a power-of-two table (mask), else
 // f(std::false_type{}) (Barrett).  Inside `[&](auto P) { ... }` the constant is P.value.
 template <class F>
+static inline int with_pow2(bool pow2, F &&f)
+{
+    if (pow2) return f(std::true_type{});
+    return f(std::false_type{});
+}
+template <class F>
 static inline int with_pow2(const psk_sketch *s, F &&f)
 {
-    if (s->pow2) return f(std::true_type{});
-    return f(std::false_type{});
+    return with_pow2(s->pow2, std::forward<F>(f));
 }
 
 PSK_HIDDEN int check_hashes_width(const psk_sketch *s, int layout, uint32_t key_len);

@@ -32,7 +32,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native as N
-from ._base import _raw_stream, _resolve_device
+from ._base import DeviceResident, _resolve_device, as_bool, equal_groups, require_device, result_buffer
 from .exceptions import CuckooFilterFullError, InitializationError, NativeLibraryError, NotSupportedError
 from .hashes import KeyT, fnv_1a
 from .keys import KeyBatch, pack_keys
@@ -83,7 +83,7 @@ def _is_default_hash(hash_function) -> bool:
     return False
 
 
-class CuckooFilter:
+class CuckooFilter(DeviceResident):
     """Cuckoo filter with the buckets in GPU memory; same surface as the reference's class plus the batch calls.
 
     Args:
@@ -97,6 +97,8 @@ class CuckooFilter:
         hash_function (function): ``None`` or ``fnv_1a``; anything else raises :class:`NotSupportedError`
         device: HIP device index (default: torch's current device)
     """
+
+    _NOUN = "filter"
 
     def __init__(self, capacity: int = 10000, bucket_size: int = 4, max_swaps: int = 500, expansion_rate: int = 2, auto_expand: bool = True,
                  finger_size: int = 4, filepath=None, hash_function=None, device=None):
@@ -248,10 +250,6 @@ class CuckooFilter:
     def hash_function(self):
         return self._hash_func
 
-    @property
-    def device(self) -> int:
-        return self._device
-
     def load_factor(self) -> float:
         """float: How full the Cuckoo Filter is currently"""
         return self.elements_added / (self.capacity * self.bucket_size)
@@ -269,27 +267,22 @@ class CuckooFilter:
             self._check_limits()
 
     # ------------------------------------------------------------------ the table
-    def _dev(self) -> str:
-        return f"cuda:{self._device}"
-
     def _alloc(self) -> None:
         """buckets and fill in HBM.  No device, no table: every call that needs one raises (there is no CPU fallback)"""
         if self._buckets is not None:
             return
-        N.lib()
-        if torch is None or N.device_count() == 0 or not torch.cuda.is_available():
-            raise NativeLibraryError("no HIP device available: the cuckoo filter's buckets live in GPU memory and there is no CPU fallback")
+        require_device("the cuckoo filter's buckets live in GPU memory")
         if self._pending is not None:
             rows, fill = self._pending
-            self._buckets = torch.from_numpy(rows.view(np.int32)).to(self._dev())
-            self._fill = torch.from_numpy(fill.view(np.int32)).to(self._dev())
+            self._buckets = torch.from_numpy(rows.view(np.int32)).to(self._dev)
+            self._fill = torch.from_numpy(fill.view(np.int32)).to(self._dev)
             self._pending = None
         else:
             self._new_table()
 
     def _new_table(self) -> None:
-        self._buckets = torch.zeros((self._capacity, self._bucket_size), dtype=torch.int32, device=self._dev())
-        self._fill = torch.zeros(self._capacity, dtype=torch.int32, device=self._dev())
+        self._buckets = torch.zeros((self._capacity, self._bucket_size), dtype=torch.int32, device=self._dev)
+        self._fill = torch.zeros(self._capacity, dtype=torch.int32, device=self._dev)
         self._marks = None
 
     @property
@@ -304,15 +297,9 @@ class CuckooFilter:
         self._alloc()
         return self._fill
 
-    @property
-    def _stream(self):
-        if _raw_stream is not None:
-            return _raw_stream(self._device) or None
-        return torch.cuda.current_stream(self._device).cuda_stream or None
-
     def synchronize(self) -> None:
         self._alloc()
-        torch.cuda.current_stream(self._device).synchronize()
+        super().synchronize()
 
     def _geom(self):
         return (self._capacity, self._bucket_size)
@@ -354,10 +341,6 @@ class CuckooFilter:
         self._elements_added = int(fill.sum())
 
     # ------------------------------------------------------------------ keys -> triples
-    def _check_batch(self, b: KeyBatch) -> None:
-        if b.where == N.DEVICE and b.device is not None and b.device != self._device:
-            raise ValueError(f"key batch lives on cuda:{b.device}, the filter on cuda:{self._device}")
-
     @staticmethod
     def _as_batch(keys) -> KeyBatch:
         if isinstance(keys, KeyBatch):
@@ -369,22 +352,16 @@ class CuckooFilter:
     def _triples(self, keys):
         """-> int32 device tensor (3, n): fingerprints, idx_1, idx_2 (uint32 bit patterns) in stream order"""
         self._alloc()
-        b = self._as_batch(keys)
-        self._check_batch(b)
-        L = N.lib()
-        if b.where == N.DEVICE:
-            out = torch.empty((3, b.n), dtype=torch.int32, device=self._dev())
-            N.check(L.psk_ck_triples(self._capacity, self._fingerprint_size, *b.args(), N.DEVICE, out.data_ptr(), self._device, self._stream))
-            return out
-        out = np.empty((3, b.n), dtype=np.uint32)
-        N.check(L.psk_ck_triples(self._capacity, self._fingerprint_size, *b.args(), N.HOST, out.ctypes.data if b.n else None, self._device, self._stream))
-        return torch.from_numpy(out.view(np.int32)).to(self._dev())
+        b = self._same_device(self._as_batch(keys))
+        addr, fin = result_buffer(b.where, (3, b.n), np.int32, torch.int32, self._device)
+        N.check(N.lib().psk_ck_triples(self._capacity, self._fingerprint_size, *b.args(), b.where, addr, self._device, self._stream))
+        return fin() if b.where == N.DEVICE else torch.from_numpy(fin()).to(self._dev)
 
     def _triples_of_fingerprints(self, fps):
         """fingerprints (int32 bit patterns, device) -> their triples at the CURRENT capacity"""
         n = int(fps.numel())
         rows = (fps.to(torch.int64) & 0xFFFFFFFF).contiguous()
-        out = torch.empty((3, n), dtype=torch.int32, device=self._dev())
+        out = torch.empty((3, n), dtype=torch.int32, device=self._dev)
         if n:
             N.check(N.lib().psk_ck_triples(self._capacity, 32, N.KEYS_HASHES, rows.data_ptr(), None, n, 1, N.DEVICE, out.data_ptr(), self._device, self._stream))
         return out
@@ -397,7 +374,7 @@ class CuckooFilter:
 
     def _present(self, tr):
         n = int(tr.shape[1])
-        out = torch.empty(n, dtype=torch.uint8, device=self._dev())
+        out = torch.empty(n, dtype=torch.uint8, device=self._dev)
         if n:
             N.check(self._present_entry()(*self._geom(), *self._table(), tr.data_ptr(), n, out.data_ptr(), self._device, self._stream))
         return out.view(torch.bool)
@@ -430,11 +407,8 @@ class CuckooFilter:
     def _survivors(self, tr):
         """the keys an ``add`` loop would insert: first occurrence of their fingerprint in the batch, fingerprint not in the table
         -> (their triples, their positions in the batch)"""
-        n = int(tr.shape[1])
-        order = torch.sort(tr[0], stable=True)
-        first = torch.ones(n, dtype=torch.bool, device=tr.device)
-        first[1:] = order.values[1:] != order.values[:-1]
-        keep = torch.zeros(n, dtype=torch.bool, device=tr.device)
+        order, first = equal_groups(tr[0])
+        keep = torch.zeros(int(tr.shape[1]), dtype=torch.bool, device=tr.device)
         keep[order.indices] = first
         keep &= ~self._present(tr)
         at = torch.nonzero(keep).reshape(-1)
@@ -449,7 +423,7 @@ class CuckooFilter:
         w = int(window.shape[1])
         if w == 0:
             return 0
-        L, dev = N.lib(), self._dev()
+        L, dev = N.lib(), self._dev
         j2 = torch.arange(w, dtype=torch.int64, device=dev) << 1
         claims = torch.cat([(window[1].to(torch.int64) << 32) | j2, (window[2].to(torch.int64) << 32) | j2 | 1])
         order = torch.sort(claims)
@@ -477,7 +451,7 @@ class CuckooFilter:
 
     def _sequential(self, tr, start: int, end: int, dedup: bool, mt, counts=None):
         """-> (status, first key not done, what the failed walk left over, keys that walked)"""
-        res = torch.zeros(12, dtype=torch.int32, device=self._dev())
+        res = torch.zeros(12, dtype=torch.int32, device=self._dev)
         walked, stats, t0 = 0, self.last_insert_stats, time.perf_counter()
         while True:  # one launch, or as many as a walk that outlives the launch's budget needs: `res` carries it from one to the next
             self._insert_launch(tr, start, end, dedup, mt, res, counts)
@@ -539,10 +513,10 @@ class CuckooFilter:
         """cuckoo.py:455-481: [leftover] + every fingerprint in bucket then slot order, re-inserted into a table `expansion_rate` times as large"""
         self._alloc()
         B = self._bucket_size
-        live = torch.arange(B, dtype=torch.int32, device=self._dev())[None, :] < self._fill[:, None]
+        live = torch.arange(B, dtype=torch.int32, device=self._dev)[None, :] < self._fill[:, None]
         fps = self._buckets[live]
         if leftover is not None:
-            fps = torch.cat([torch.tensor([leftover if leftover < 2**31 else leftover - 2**32], dtype=torch.int32, device=self._dev()), fps])
+            fps = torch.cat([torch.tensor([leftover if leftover < 2**31 else leftover - 2**32], dtype=torch.int32, device=self._dev), fps])
         capacity = self._capacity * self._expansion_rate
         if not isinstance(capacity, int) or capacity < 1 or capacity >= 2**31:
             raise NotSupportedError(f"CuckooFilter: cannot expand to a capacity of {capacity}")
@@ -556,7 +530,7 @@ class CuckooFilter:
         """run `body(mt)` between ``random.getstate()`` and ``random.setstate()``: the state is read before the table is first written"""
         self._alloc()
         state = random.getstate()
-        mt = torch.from_numpy(state_to_words(state).view(np.int32)).to(self._dev())
+        mt = torch.from_numpy(state_to_words(state).view(np.int32)).to(self._dev)
         self.last_insert_stats = {}
         try:
             body(mt)
@@ -581,17 +555,15 @@ class CuckooFilter:
     # ------------------------------------------------------------------ lookup / removal
     def check_many(self, keys):
         """bool per key (numpy for host keys, a torch tensor for device keys)"""
+        return as_bool(self._lookup(N.lib().psk_ck_check, keys, np.uint8, torch.uint8))
+
+    def _lookup(self, entry, keys, np_dtype, torch_dtype):
+        """``psk_ck_check`` / ``psk_cck_check``: one answer per key, where the keys are"""
         self._alloc()
-        b = self._as_batch(keys)
-        self._check_batch(b)
-        args = (*self._geom(), self._fingerprint_size, *self._table(), *b.args())
-        if b.where == N.DEVICE:
-            out = torch.empty(b.n, dtype=torch.uint8, device=self._dev())
-            N.check(N.lib().psk_ck_check(*args, N.DEVICE, out.data_ptr(), self._device, self._stream))
-            return out.view(torch.bool)
-        out = np.empty(b.n, dtype=np.uint8)
-        N.check(N.lib().psk_ck_check(*args, N.HOST, out.ctypes.data if b.n else None, self._device, self._stream))
-        return out.view(np.bool_)
+        b = self._same_device(self._as_batch(keys))
+        addr, fin = result_buffer(b.where, b.n, np_dtype, torch_dtype, self._device)
+        N.check(entry(*self._geom(), self._fingerprint_size, *self._table(), *b.args(), b.where, addr, self._device, self._stream))
+        return fin()
 
     def check(self, key: KeyT) -> bool:
         """Check if an element is in the filter (cuckoo.py:306-315)"""
@@ -603,22 +575,20 @@ class CuckooFilter:
         on_device = b.where == N.DEVICE
         tr = self._triples(b)
         n = int(tr.shape[1])
-        out = torch.zeros(n, dtype=torch.uint8, device=self._dev())
+        out = torch.zeros(n, dtype=torch.uint8, device=self._dev)
         if n:
             # how many earlier requests carry the same fingerprint: position inside the fingerprint's group of a stable sort
-            order = torch.sort(tr[0], stable=True)
+            order, first = equal_groups(tr[0])
             idx = torch.arange(n, dtype=torch.int64, device=tr.device)
-            first = torch.ones(n, dtype=torch.bool, device=tr.device)
-            first[1:] = order.values[1:] != order.values[:-1]
             group_start = torch.cummax(torch.where(first, idx, torch.zeros_like(idx)), 0).values
             rank = torch.empty(n, dtype=torch.int32, device=tr.device)
             rank[order.indices] = (idx - group_start).to(torch.int32)
             if self._marks is None:
-                self._marks = torch.zeros(self._capacity, dtype=torch.int32, device=self._dev())
+                self._marks = torch.zeros(self._capacity, dtype=torch.int32, device=self._dev)
             N.check(N.lib().psk_ck_remove(*self._geom(), *self._table(), tr.data_ptr(), rank.data_ptr(), n, self._marks.data_ptr(), out.data_ptr(), self._device,
                                           self._stream))
             self._elements_added -= int(out.sum().item())
-        return out.view(torch.bool) if on_device else out.cpu().numpy().view(np.bool_)
+        return as_bool(out if on_device else out.cpu().numpy())
 
     def remove(self, key: KeyT) -> bool:
         """Remove an element from the filter (cuckoo.py:317-330)"""

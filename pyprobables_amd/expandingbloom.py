@@ -27,6 +27,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native as N
+from ._base import as_bool
 from .bloom import BloomFilter, _existing_file
 from .exceptions import RotatingBloomFilterError
 from .hashes import HashFuncT, HashResultsT, KeyT, default_fnv_1a
@@ -115,7 +116,7 @@ class ExpandingBloomFilter:
     def _k(self) -> int:
         return self._blooms[-1].number_hashes
 
-    def _dev(self) -> int:
+    def _device_index(self) -> int:
         return self._blooms[-1].device
 
     def _stream(self):
@@ -125,7 +126,7 @@ class ExpandingBloomFilter:
         """device scratch that only ever grows (torch owns the memory; the kernels are ours)"""
         t = self._scratch.get(name)
         if t is None or t.numel() < count:
-            t = torch.empty(max(count, 1), dtype=dtype, device=f"cuda:{self._dev()}")
+            t = torch.empty(max(count, 1), dtype=dtype, device=f"cuda:{self._device_index()}")
             if fill is not None:
                 t.fill_(fill)
             self._scratch[name] = t
@@ -146,12 +147,12 @@ class ExpandingBloomFilter:
         k, L = self._k, N.lib()
         for j, f in enumerate(self._blooms):
             N.check(L.psk_idx_test(f.table_tensor.data_ptr(), idx.data_ptr() + 4 * start * k, count, k, out.data_ptr(),
-                                   1 if j else 0, self._dev(), self._stream()))
+                                   1 if j else 0, self._device_index(), self._stream()))
         return out[:count]
 
     def _insert(self, blm: BloomFilter, idx, start: int, count: int, flag) -> None:
         N.check(N.lib().psk_idx_insert(blm.table_tensor.data_ptr(), idx.data_ptr() + 4 * start * self._k,
-                                       flag.data_ptr() if flag is not None else None, count, self._k, self._dev(),
+                                       flag.data_ptr() if flag is not None else None, count, self._k, self._device_index(),
                                        self._stream()))
 
     _SUB = 1 << 18  # keys per resolution step: the scratch is a hash map over the clear bits ONE step touches (see _resolve_insert)
@@ -175,8 +176,8 @@ class ExpandingBloomFilter:
         for s in range(0, count, self._SUB):
             n = min(self._SUB, count - s)
             N.check(L.psk_idx_resolve_ordered_hashed(tab, idx.data_ptr() + 4 * (start + s) * k, (present.data_ptr() + s) if present is not None else None,
-                                                    n, k, slots.data_ptr(), lg, flag.data_ptr(), cnt.data_ptr(), self._dev(), self._stream()))
-            N.check(L.psk_idx_insert(tab, idx.data_ptr() + 4 * (start + s) * k, flag.data_ptr(), n, k, self._dev(), self._stream()))
+                                                    n, k, slots.data_ptr(), lg, flag.data_ptr(), cnt.data_ptr(), self._device_index(), self._stream()))
+            N.check(L.psk_idx_insert(tab, idx.data_ptr() + 4 * (start + s) * k, flag.data_ptr(), n, k, self._device_index(), self._stream()))
         inserted, full = (int(x) for x in cnt.tolist())
         if full:  # (a map of twice the step's probes cannot fill: a guard, not a path)
             raise RuntimeError("stacked filter: the resolution map overflowed")
@@ -323,12 +324,10 @@ class ExpandingBloomFilter:
 
     def _check_batch(self, b: KeyBatch):
         if b.n == 0:
-            return np.zeros(0, dtype=np.bool_) if b.where != N.DEVICE else torch.zeros(0, dtype=torch.bool, device=f"cuda:{self._dev()}")
+            return np.zeros(0, dtype=np.bool_) if b.where != N.DEVICE else torch.zeros(0, dtype=torch.bool, device=f"cuda:{self._device_index()}")
         idx = self._indices(b)
         res = self._present(idx, 0, b.n).clone()
-        if b.where == N.DEVICE:
-            return res.view(torch.bool)
-        return res.cpu().numpy().view(np.bool_)
+        return as_bool(res if b.where == N.DEVICE else res.cpu().numpy())
 
     def check_many(self, keys):
         """membership of every key in ANY filter of the stack: numpy bool[n] (host keys) / torch bool[n] (device keys)"""

@@ -18,6 +18,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _native as N
+from ._base import result_buffer
 
 try:  # torch is plumbing: device buffers + streams
     import torch
@@ -315,10 +316,21 @@ def digest_batch(keys, algo: int, depth: int, device: int, stream=None) -> KeyBa
     b = _pack_bytes_utf8(keys)
     if b.layout not in (N.KEYS_FIXED, N.KEYS_VARLEN8):
         raise TypeError("digest families hash bytes")
+    addr, fin = result_buffer(b.where, (b.n, depth), np.uint64, getattr(torch, "int64", None), device)
+    N.check(N.lib().psk_digest_chain(algo, *b.args(), depth, b.where, addr, device, stream))
+    out = fin()
     if b.where == N.DEVICE:
-        out = torch.empty((b.n, depth), dtype=torch.int64, device=f"cuda:{device}")
-        N.check(N.lib().psk_digest_chain(algo, *b.args(), depth, N.DEVICE, out.data_ptr(), device, stream))
         return KeyBatch(N.KEYS_HASHES, out.data_ptr() if b.n else 0, 0, b.n, depth, N.DEVICE, device, [out, *b.keep])
-    out = np.empty((b.n, depth), dtype=np.uint64)
-    N.check(N.lib().psk_digest_chain(algo, *b.args(), depth, N.HOST, out.ctypes.data if out.size else None, device, stream))
     return KeyBatch(N.KEYS_HASHES, _np_ptr(out) if out.size else 0, 0, b.n, depth, N.HOST, None, [out])
+
+
+def hashed_batch(keys, hash_func, fused: bool, digest, depth: int, device: int, stream) -> KeyBatch:
+    """the way a ``hash_function`` travels: the fused FNV family as keys (the kernels hash them), default_md5 / default_sha256
+    (``digest``: ``hashes.device_digest``) as digest chains computed on the device, anything else evaluated here, on the host, per key"""
+    if fused:
+        return pack_keys(keys)
+    if digest is not None:
+        return digest_batch(keys, digest, depth, device, stream)
+    if _is_key(keys):
+        keys = [keys]
+    return pack_hashes([hash_func(k, depth) for k in keys] if len(keys) else np.zeros((0, depth), dtype=np.uint64), depth)

@@ -21,6 +21,7 @@ import os
 import weakref
 
 from . import _native as N
+from ._base import current_stream
 
 try:
     import torch
@@ -41,8 +42,7 @@ def hip_or_reduce(dst, src, nslices: int, slice_words: int) -> None:
     """dst[w] = OR_j src[j*slice_words + w] on the GPU (the engine's kernel; device tensors only)"""
     if not (dst.is_cuda and src.is_cuda):
         raise RuntimeError("hip_or_reduce needs device tensors (there is no CPU fallback)")
-    stream = torch.cuda.current_stream(dst.device).cuda_stream or None
-    N.check(N.lib().psk_or_reduce_slices(dst.data_ptr(), src.data_ptr(), nslices, slice_words, dst.device.index, stream))
+    N.check(N.lib().psk_or_reduce_slices(dst.data_ptr(), src.data_ptr(), nslices, slice_words, dst.device.index, current_stream(dst.device.index)))
 
 
 _merge_bufs: dict = {}

@@ -36,10 +36,10 @@ from collections.abc import Iterator
 import numpy as np
 
 from . import _native as N
-from ._base import _raw_stream, _resolve_device
-from .exceptions import NativeLibraryError, NotSupportedError, QuotientFilterError
+from ._base import DeviceResident, _resolve_device, as_bool, equal_groups, require_device, result_buffer
+from .exceptions import NotSupportedError, QuotientFilterError
 from .hashes import KeyT, fnv_1a_32
-from .keys import KeyBatch, pack_keys
+from .keys import pack_keys
 
 try:
     import torch
@@ -155,7 +155,7 @@ def _is_default_hash(hash_function) -> bool:
     return False
 
 
-class QuotientFilter:
+class QuotientFilter(DeviceResident):
     """Quotient filter with the table in GPU memory; same surface as the reference's class plus the batch calls.
 
     Args:
@@ -167,6 +167,8 @@ class QuotientFilter:
     Raises:
         QuotientFilterError: Raised when unable to initialize
     """
+
+    _NOUN = "filter"
 
     def __init__(self, quotient: int = 20, auto_expand: bool = True, hash_function=None, device=None):
         _check_quotient(quotient)
@@ -189,10 +191,8 @@ class QuotientFilter:
         parameters and properties above exist without one."""
         if self._filter is not None:
             return
-        N.lib()
-        if torch is None or N.device_count() == 0 or not torch.cuda.is_available():
-            raise NativeLibraryError("no HIP device available: the quotient filter's table lives in GPU memory and there is no CPU fallback")
-        dev = f"cuda:{self._device}"
+        require_device("the quotient filter's table lives in GPU memory")
+        dev = self._dev
         dtype = {8: torch.uint8, 16: torch.int16, 32: torch.int32}[self._bits_per_elm]
         words = max(self._size // 32, 1)
         self._filter = torch.zeros(self._size, dtype=dtype, device=dev)
@@ -261,10 +261,6 @@ class QuotientFilter:
     def hash_function(self):
         return self._hash_func
 
-    @property
-    def device(self) -> int:
-        return self._device
-
     # the four arrays as they lie in HBM (include/psk.h "QuotientFilter")
     @property
     def filter_tensor(self):
@@ -297,20 +293,11 @@ class QuotientFilter:
             out[name] = np.unpackbits(t.cpu().numpy().view(np.uint8), bitorder="little")[: self._size]
         return out
 
-    @property
-    def _stream(self):
-        if _raw_stream is not None:
-            return _raw_stream(self._device) or None
-        return torch.cuda.current_stream(self._device).cuda_stream or None
-
     def synchronize(self) -> None:
         self._alloc()
-        torch.cuda.current_stream(self._device).synchronize()
+        super().synchronize()
 
     # ------------------------------------------------------------------ hashes in, as uint32 bit patterns in int32 device tensors
-    def _dev(self) -> str:
-        return f"cuda:{self._device}"
-
     def _hash_keys(self, keys):
         """keys -> (int32 device tensor of the 32-bit hashes in stream order)"""
         self._alloc()
@@ -318,25 +305,16 @@ class QuotientFilter:
             if isinstance(keys, (str, bytes, bytearray, memoryview)):
                 keys = [keys]
             return self._as_bits(np.fromiter((int(self._hash_func(k, 0)) & 0xFFFFFFFF for k in keys), dtype=np.uint64))
-        b = pack_keys(keys)
-        self._check_batch(b)
-        if b.where == N.DEVICE:
-            out = torch.empty(b.n, dtype=torch.int32, device=self._dev())
-            N.check(N.lib().psk_qf_hash(*b.args(), N.DEVICE, out.data_ptr(), self._device, self._stream))
-            return out
-        out = np.empty(b.n, dtype=np.uint32)
-        N.check(N.lib().psk_qf_hash(*b.args(), N.HOST, out.ctypes.data if b.n else None, self._device, self._stream))
-        return torch.from_numpy(out.view(np.int32)).to(self._dev())
-
-    def _check_batch(self, b: KeyBatch) -> None:
-        if b.where == N.DEVICE and b.device is not None and b.device != self._device:
-            raise ValueError(f"key batch lives on cuda:{b.device}, the filter on cuda:{self._device}")
+        b = self._same_device(pack_keys(keys))
+        addr, fin = result_buffer(b.where, b.n, np.int32, torch.int32, self._device)
+        N.check(N.lib().psk_qf_hash(*b.args(), b.where, addr, self._device, self._stream))
+        return fin() if b.where == N.DEVICE else torch.from_numpy(fin()).to(self._dev)
 
     def _as_bits(self, hashes):
         """ints / numpy / torch (any integer type holding 0 .. 2^32 - 1) -> int32 device tensor of the bit patterns"""
         self._alloc()
         if torch is not None and isinstance(hashes, torch.Tensor):
-            t = hashes.to(self._dev()).reshape(-1)
+            t = hashes.to(self._dev).reshape(-1)
             if t.dtype == torch.int32:
                 return t.contiguous()
             t = t.to(torch.int64) & 0xFFFFFFFF
@@ -345,7 +323,7 @@ class QuotientFilter:
             hashes = [hashes]
         a = np.asarray(hashes if isinstance(hashes, np.ndarray) else [int(h) & 0xFFFFFFFF for h in hashes], dtype=np.uint64)
         a = (a.reshape(-1) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-        return torch.from_numpy(a.view(np.int32)).to(self._dev())
+        return torch.from_numpy(a.view(np.int32)).to(self._dev)
 
     @staticmethod
     def _usort(bits, unique: bool):
@@ -363,7 +341,7 @@ class QuotientFilter:
     def _build(self, sorted_bits) -> None:
         self._alloc()
         n = int(sorted_bits.numel())
-        scratch = torch.empty(n // 1024 + 2, dtype=torch.int32, device=self._dev())
+        scratch = torch.empty(n // 1024 + 2, dtype=torch.int32, device=self._dev)
         N.check(N.lib().psk_qf_build(self._q, sorted_bits.data_ptr() if n else None, n, self._filter.data_ptr(), self._occ.data_ptr(),
                                      self._cont.data_ptr(), self._sh.data_ptr(), scratch.data_ptr(), self._device, self._stream))
         self._held = n
@@ -376,14 +354,14 @@ class QuotientFilter:
         """-> (hashes of the table ascending, int32 bit patterns on the device; first empty slot or None)"""
         n = self._held
         if n == 0:
-            return torch.empty(0, dtype=torch.int32, device=self._dev()), 0
+            return torch.empty(0, dtype=torch.int32, device=self._dev), 0
         words = int(self._occ.numel())
-        counts = torch.empty((3, words), dtype=torch.int64, device=self._dev())
-        marks = torch.empty(2, dtype=torch.int32, device=self._dev())
+        counts = torch.empty((3, words), dtype=torch.int64, device=self._dev)
+        marks = torch.empty(2, dtype=torch.int32, device=self._dev)
         L = N.lib()
         N.check(L.psk_qf_decode(*self._table_args(), counts.data_ptr(), marks.data_ptr(), None, 0, self._device, self._stream))
         inc = torch.cumsum(counts, dim=1).contiguous()
-        out = torch.empty(n, dtype=torch.int32, device=self._dev())
+        out = torch.empty(n, dtype=torch.int32, device=self._dev)
         N.check(L.psk_qf_decode(*self._table_args(), inc.data_ptr(), marks.data_ptr(), out.data_ptr(), n, self._device, self._stream))
         first_empty = int(marks[1].item()) & 0xFFFFFFFF
         return self._usort(out, unique=False), (None if first_empty == 0xFFFFFFFF else first_empty)
@@ -425,7 +403,7 @@ class QuotientFilter:
         limit = resize_threshold(q, self._max_load_factor) if self._auto_resize else self._size
         if held + n + stale >= limit:
             # close to the threshold (or the last slot): the exact count of new hashes decides, and psk_qf_check_alt gives it
-            present = torch.empty(n, dtype=torch.uint8, device=self._dev())
+            present = torch.empty(n, dtype=torch.uint8, device=self._dev)
             N.check(N.lib().psk_qf_check_alt(*self._table_args(), batch.data_ptr(), n, present.data_ptr(), self._device, self._stream))
             batch = batch[present == 0]
             n = int(batch.numel())
@@ -439,7 +417,7 @@ class QuotientFilter:
                 return True
         # (else: even if every hash of the batch is new the quotient stays and slots remain; hashes in the table already are no-ops of the kernels)
         scratch = self._take_scratch(n)
-        result = torch.empty(2, dtype=torch.int32, device=self._dev())
+        result = torch.empty(2, dtype=torch.int32, device=self._dev)
         N.check(N.lib().psk_qf_add_alt(*self._table_args(), batch.data_ptr(), n, scratch.data_ptr(), result.data_ptr(), self._device, self._stream))
         added, status = result.tolist()
         self._remove_scratch = scratch
@@ -453,7 +431,7 @@ class QuotientFilter:
         that fails may leave bits behind: only a call that ran gives it back"""
         words = int(self._occ.numel())
         if self._remove_scratch is None or int(self._remove_scratch.numel()) < 2 * words + 2 + n:
-            self._remove_scratch = torch.zeros(2 * words + 2 + max(n, 1024), dtype=torch.int32, device=self._dev())
+            self._remove_scratch = torch.zeros(2 * words + 2 + max(n, 1024), dtype=torch.int32, device=self._dev)
         scratch, self._remove_scratch = self._remove_scratch, None
         return scratch
 
@@ -466,10 +444,7 @@ class QuotientFilter:
         q = self._q
         if self._auto_resize and total + stale >= resize_threshold(q, self._max_load_factor):
             # the threshold is reached inside this stream: whether (and how often) the table doubles depends on WHERE
-            key = bits ^ _I32_MIN
-            order = torch.sort(key, stable=True)
-            first = torch.ones(m, dtype=torch.bool, device=bits.device)
-            first[1:] = order.values[1:] != order.values[:-1]
+            order, first = equal_groups(bits ^ _I32_MIN)
             if old is not None:
                 first &= ~torch.isin(order.values, old ^ _I32_MIN)
             new = torch.zeros(m, dtype=torch.int64, device=bits.device)
@@ -529,7 +504,7 @@ class QuotientFilter:
 
     def _remove_local(self, gone) -> int:
         n = int(gone.numel())
-        count = torch.empty(1, dtype=torch.int32, device=self._dev())
+        count = torch.empty(1, dtype=torch.int32, device=self._dev)
         scratch = self._take_scratch(n)
         N.check(N.lib().psk_qf_remove_alt(*self._table_args(), gone.data_ptr(), n, scratch.data_ptr(), count.data_ptr(), self._device, self._stream))
         removed = int(count.item())
@@ -559,23 +534,18 @@ class QuotientFilter:
         """bool per key (numpy for host keys, a torch tensor for device keys)"""
         if not self._fused:
             return self.check_alt_many(self._hash_keys(keys).cpu().numpy().view(np.uint32))
-        b = pack_keys(keys)
-        self._check_batch(b)
-        if b.where == N.DEVICE:
-            out = torch.empty(b.n, dtype=torch.uint8, device=self._dev())
-            N.check(N.lib().psk_qf_check(*self._table_args(), *b.args(), N.DEVICE, out.data_ptr(), self._device, self._stream))
-            return out.view(torch.bool)
-        out = np.empty(b.n, dtype=np.uint8)
-        N.check(N.lib().psk_qf_check(*self._table_args(), *b.args(), N.HOST, out.ctypes.data if b.n else None, self._device, self._stream))
-        return out.view(np.bool_)
+        b = self._same_device(pack_keys(keys))
+        addr, fin = result_buffer(b.where, b.n, np.uint8, torch.uint8, self._device)
+        N.check(N.lib().psk_qf_check(*self._table_args(), *b.args(), b.where, addr, self._device, self._stream))
+        return as_bool(fin())
 
     def check_alt_many(self, hashes):
         on_device = torch is not None and isinstance(hashes, torch.Tensor) and hashes.is_cuda
         bits = self._as_bits(hashes)
-        out = torch.empty(bits.numel(), dtype=torch.uint8, device=self._dev())
+        out = torch.empty(bits.numel(), dtype=torch.uint8, device=self._dev)
         N.check(N.lib().psk_qf_check_alt(*self._table_args(), bits.data_ptr() if bits.numel() else None, bits.numel(), out.data_ptr(), self._device,
                                          self._stream))
-        return out.view(torch.bool) if on_device else out.cpu().numpy().view(np.bool_)
+        return as_bool(out if on_device else out.cpu().numpy())
 
     def check(self, key: KeyT) -> bool:
         """Check to see if key is likely in the quotient filter (quotientfilter.py:187-195)"""
@@ -612,7 +582,7 @@ class QuotientFilter:
         if self._hash_func("test", 0) != second._hash_func("test", 0):
             raise QuotientFilterError("Hash functions do not match")
         theirs = second._reference_order() if isinstance(second, QuotientFilter) else self._as_bits(list(second.hashes()))
-        self._add_bits(theirs.to(self._dev()))
+        self._add_bits(theirs.to(self._dev))
 
     def validate_metadata(self, verbose=False) -> bool:
         """Check for invalid bit settings: a continuation that is not shifted (quotientfilter.py:521-538 names both such rows)"""
