@@ -454,6 +454,30 @@ int psk_bank_match(const void *slices_dev, uint64_t filters, uint64_t m_bits, ui
                    uint64_t n, uint32_t key_len, int where, uint32_t *mask_dev, uint32_t *count_dev, const uint64_t *out_offsets_dev,
                    uint32_t *ids_dev, int device, void *stream);
 
+/* Bank statistics: the filters of a bank as sets -- what the reference answers per object, for every row (pair, group) in one launch.
+ * No handle: tables, id lists, seg / members and outputs are device memory owned by the caller; tables and dst are 16-byte aligned.  Enqueue
+ * only, on `stream`.  Rows are read whole (psk_bank_row_bytes): the pad bits of a row are never set.  An id at or beyond its table counts as
+ * an empty row (as psk_bank_check answers 0).  Byte and element offsets are 64-bit: filters * row_bytes and na * nb may pass 2^32.
+ *   popcount  out[i] = the set bits of row ids[i] (bloom.py:340-352's _cnt_number_bits_set, the input of estimate_elements); ids_dev == NULL:
+ *             row i, and n == filters is required.  n == 0 launches nothing; more rows than the grid holds are walked with a stride.
+ *   overlap   out[i * nb + j] = popcount(row a_ids[i] of A AND row b_ids[j] of B), uint32[na][nb] row-major: count_int of bloom.py:448-457
+ *             (jaccard_index) for every pair; count_union = popcount(a) + popcount(b) - count_int.  NULL id lists mean rows 0 .. na - 1 /
+ *             0 .. nb - 1, and then na <= filters_a / nb <= filters_b is required.  Ids may repeat and come in any order.  m_bits == 2^31 is
+ *             accepted: the counts fit the unsigned word.  Same table, same id list (both NULL, or one pointer) and na == nb: only the tiles
+ *             on or above the diagonal are computed, each stored at both places.  na, nb < 2^32.  
+ *   reduce    row g of dst (`groups` rows of the table's row size) = the OR (op 0: bloom.py:401-428 union, chained) or the AND (op 1:
+ *             bloom.py:371-399 intersection, chained) of the source rows members[seg[g] .. seg[g + 1]); seg = uint64[groups + 1],
+ *             non-decreasing.  Rows are STORED, not ORed in.  bits_dev[g] (uint64, may be NULL) = the popcount of the stored row: what
+ *             bloom.py:398 / 427 feed to estimate_elements.  An empty group stores a zero row under either op.  dst overlapping src, or
+ *             any other op: PSK_EINVAL. */
+int psk_bank_popcount(const void *table_dev, uint64_t filters, uint64_t m_bits, const uint32_t *ids_dev, uint64_t n, uint64_t *out_dev,
+                      int device, void *stream);
+int psk_bank_overlap(const void *table_a_dev, uint64_t filters_a, const uint32_t *a_ids_dev, uint64_t na, const void *table_b_dev,
+                     uint64_t filters_b, const uint32_t *b_ids_dev, uint64_t nb, uint64_t m_bits, uint32_t *out_dev, int device,
+                     void *stream);
+int psk_bank_reduce(const void *src_dev, uint64_t filters, uint64_t m_bits, const uint64_t *seg_dev, const uint32_t *members_dev,
+                    uint64_t groups, int op, void *dst_dev, uint64_t *bits_dev, int device, void *stream);
+
 /* ------------------------------------------------------------ CuckooFilter
  * cuckoo/cuckoo.py: `capacity` buckets of `bucket_size` fingerprints of `fp_bits` bits.  No handle: the caller owns (device memory)
  *   buckets   uint32[capacity][bucket_size], every row filled from the left, its unused slots 0 (an export is this array plus the footer)

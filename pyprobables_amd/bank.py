@@ -11,11 +11,16 @@ an LDS image of the row and ORs the image into the table once (``psk_bank_build`
 "Which filters may hold this key?" is answered from a second copy of the table, the *slice image*: the bank transposed (``psk_bank_slices``),
 row ``p`` holding bit ``p`` of every filter.  All filters share the geometry and the hash family, so the answer for one key is the AND of
 its k slice rows (``psk_bank_match``).  The image is allocated on the first match and refreshed lazily: updates only mark it stale.
+
+The filters as sets are read from the table alone: ``bits_set`` / ``estimate_elements`` (``psk_bank_popcount``), ``overlap`` /
+``jaccard`` for all pairs of two lists of filters (``psk_bank_overlap``: a tiled GEMM over AND and popcount), and ``reduce``, the union or
+intersection of groups of filters as a new bank (``psk_bank_reduce``).
 """
 
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -40,6 +45,9 @@ BANK_ROUTE_R = 16           # kBankRouteR of csrc/psk_bank.hip: route 0 takes th
 BANK_LDS_ROW_BYTES = 65536  # rows beyond it never take the LDS image
 BANK_MATCH_MAX_HASHES = 64  # psk_bank_match keeps a workgroup's k * 256 bit positions in LDS: 64 KiB at the cap
 BANK_SLICE_MAX_GROUPS = 8   # more stale 32-filter column groups than this: the next match transposes the whole bank, not group by group
+BANK_OVERLAP_T = 64         # kBankOvlT: psk_bank_overlap's workgroup owns a T x T tile of pairs ...
+BANK_OVERLAP_C = 32         # kBankOvlC: ... and walks the rows in chunks of C words
+BANK_GRID_CAP = 4096        # kBankGridCap: more rows (popcount), tiles (overlap) or row pieces (reduce) than this are walked with a stride
 _ELEM = {N.KEYS_FIXED: 1, N.KEYS_VARLEN8: 1, N.KEYS_VARLEN32: 4, N.KEYS_HASHES: 8}
 
 
@@ -409,6 +417,147 @@ class BloomFilterBank(DeviceResident):
             raise TypeError("match takes one key; use match_many for a batch")
         _, ids = self._match_batch(b, "ids")
         return [int(f) for f in (ids if isinstance(ids, np.ndarray) else ids.cpu().numpy())]
+
+    # ------------------------------------------------------------------ the filters as sets: bit counts, estimates, overlap, folds
+    def _rows(self, ids, validate: bool, what: str = "ids"):
+        """a list of this bank's filters -> (n, int32 device tensor, or None for "every filter"), checked as `_ids` checks"""
+        if ids is None:
+            return self._num_filters, None
+        is_dev = torch is not None and isinstance(ids, torch.Tensor) and ids.is_cuda
+        n = int(ids.numel()) if torch is not None and isinstance(ids, torch.Tensor) else int(np.asarray(ids).size)
+        if n >= 2**32:
+            raise ValueError(f"{what} names 2^32 filters or more")
+        return n, self._ids_u32(self._ids(ids, n, N.DEVICE, validate if is_dev else True))
+
+    def _bits(self, rows, n: int):
+        out = torch.empty(n, dtype=torch.int64, device=self._dev)
+        if n == 0:
+            return out
+        N.check(N.lib().psk_bank_popcount(self._table.data_ptr(), self._num_filters, self._num_bits, None if rows is None else self._addr(rows) or None, n,
+                                          self._addr(out) or None, self._device, self._stream))
+        return out
+
+    def bits_set(self, ids=None, validate: bool = True):
+        """torch.int64[n] on the device: the number of set bits of filters ``ids`` (``None``: of every filter)"""
+        n, rows = self._rows(ids, validate)
+        return self._bits(rows, n)
+
+    def _estimates(self, bits: np.ndarray) -> np.ndarray:
+        """bloom.py:340-352 for each bit count: math.log on the host, once per distinct count (a vector log one ulp off could move the truncation)"""
+        m, k = self._num_bits, self._number_hashes
+        vals, inv = np.unique(bits, return_inverse=True)
+        est = [-1 if int(c) >= m else int(-1 * (float(m) / float(k)) * math.log(1 - (float(int(c)) / float(m)))) for c in vals]
+        return np.array(est, dtype=np.int64)[inv].reshape(bits.shape)
+
+    def estimate_elements(self, ids=None, validate: bool = True) -> np.ndarray:
+        """numpy int64[n]: entry i is ``bank.filter(ids[i]).estimate_elements()`` (bloom.py:340-352), -1 for a filter with every bit set"""
+        return self._estimates(self.bits_set(ids, validate).cpu().numpy())
+
+    def current_false_positive_rate(self) -> np.ndarray:
+        """numpy float64[num_filters]: bloom.py:361-369 from each filter's ``elements_added``"""
+        m, k = self._num_bits, self._number_hashes
+        vals, inv = np.unique(self.elements_added, return_inverse=True)
+        return np.array([math.pow((1 - math.exp(k * -1 * int(e) / m)), k) for e in vals], dtype=np.float64)[inv]
+
+    def _similar(self, other):
+        if other is None or other is self:
+            return self
+        if not isinstance(other, BloomFilterBank):
+            raise TypeError("other must be a BloomFilterBank")
+        if other._num_bits != self._num_bits or other._number_hashes != self._number_hashes or \
+                list(other._hash_func("test", self._number_hashes)) != list(self._hash_func("test", self._number_hashes)):
+            raise SimilarityError("the other bank's geometry or hash function differs from this bank's")
+        if other._device != self._device:
+            raise ValueError(f"the other bank lives on cuda:{other._device}, this bank on cuda:{self._device}")
+        return other
+
+    def _overlap(self, other, a, b, validate: bool):
+        """-> (other, rows a, rows b, int32[na, nb] counts); the symmetric case (one bank, one list) computes the upper triangle only"""
+        other = self._similar(other)
+        if self._num_bits >= 2**31:
+            raise NotSupportedError("overlap counts of filters of 2^31 bits do not fit the int32 tensor: call psk_bank_overlap with a uint32 buffer")
+        na, ra = self._rows(a, validate, "a")
+        if other is self and (b is a):
+            nb, rb = na, ra
+        else:
+            nb, rb = other._rows(b, validate, "b")
+        out = torch.empty((na, nb), dtype=torch.int32, device=self._dev)
+        if na and nb:
+            # (NULL lists take rows 0 .. n - 1: n == num_filters here)
+            N.check(N.lib().psk_bank_overlap(self._table.data_ptr(), self._num_filters, None if ra is None else ra.data_ptr(), na, other._table.data_ptr(),
+                                             other._num_filters, None if rb is None else rb.data_ptr(), nb, self._num_bits, out.data_ptr(), self._device,
+                                             self._stream))
+        return other, (na, ra), (nb, rb), out
+
+    def overlap(self, other=None, a=None, b=None, validate: bool = True):
+        """torch.int32[na, nb] on the device: entry (i, j) is the number of bits set in both filter ``a[i]`` of this bank and filter ``b[j]`` of
+        ``other`` (``None``: this bank; ``a`` / ``b`` of ``None``: every filter) -- ``count_int`` of bloom.py:448-457 for every pair at once.
+        ``other`` must share the geometry and the hash function (else ``SimilarityError``) and the device (else ``ValueError``)."""
+        return self._overlap(other, a, b, validate)[3]
+
+    def jaccard(self, other=None, a=None, b=None, validate: bool = True):
+        """torch.float64[na, nb] on the device: ``blm[a[i]].jaccard_index(blm[b[j]])`` (bloom.py:430-460) for every pair, bit for bit -- the
+        correctly rounded quotient of the same two integers, 1.0 where the union is empty"""
+        other, (na, ra), (nb, rb), inter = self._overlap(other, a, b, validate)
+        inter = inter.to(torch.int64)
+        ca = self._bits(ra, na)
+        cb = ca if (other is self and rb is ra and nb == na) else other._bits(rb, nb)
+        union = ca[:, None] + cb[None, :] - inter
+        return torch.where(union == 0, torch.ones((), dtype=torch.float64, device=self._dev), inter.to(torch.float64) / union.to(torch.float64).clamp_(min=1.0))
+
+    def reduce(self, groups, op: str = "or", validate: bool = True):
+        """a new bank of G filters (same geometry, hash function and device): filter g is the chained ``union`` (``op="or"``, bloom.py:401-428) or
+        ``intersection`` (``"and"``, bloom.py:371-399) of this bank's filters ``groups[g]``.  ``groups``: a list of lists of filter ids, or
+        ``(offsets[G + 1], members[total])`` arrays or tensors.  ``elements_added[g]`` of the new bank is ``estimate_elements()`` of its row (-1
+        for a full row), as the reference's union / intersection leave it.  An empty group gives an empty filter under ``"or"`` and raises
+        ``ValueError`` under ``"and"`` (unchecked device offsets: the zero row)."""
+        if op not in ("or", "and"):
+            raise ValueError(f"op must be 'or' or 'and', not {op!r}")
+        if isinstance(groups, tuple) and len(groups) == 2:
+            offs, members = groups
+        else:
+            groups = [np.asarray(g, dtype=np.int64).reshape(-1) if len(g) else np.zeros(0, dtype=np.int64) for g in groups]
+            offs = np.zeros(len(groups) + 1, dtype=np.int64)
+            np.cumsum([g.size for g in groups], out=offs[1:])
+            members = np.concatenate(groups) if groups else np.zeros(0, dtype=np.int64)
+        offs_dev = torch is not None and isinstance(offs, torch.Tensor) and offs.is_cuda
+        if offs_dev:
+            if offs.dim() != 1 or offs.numel() < 1 or offs.is_floating_point() or offs.dtype == torch.bool:
+                raise TypeError("group offsets must be a 1-D integer tensor of G + 1 entries")
+            if offs.device.index != self._device:
+                raise ValueError(f"group offsets live on cuda:{offs.device.index}, the bank on cuda:{self._device}")
+            seg = offs.to(torch.int64).contiguous()
+            total = int(members.numel()) if isinstance(members, torch.Tensor) else int(np.asarray(members).size)
+            if validate:  # one reduction, one synchronisation
+                bad = (seg[1:] < seg[:-1]).any() | (seg[0] != 0) | (seg[-1] != total)
+                empty = (seg[1:] == seg[:-1]).any()
+                bad, empty = bool(bad.item()), bool(empty.item())
+        else:
+            o = offs.numpy() if torch is not None and isinstance(offs, torch.Tensor) else np.asarray(offs)
+            if o.ndim != 1 or o.size < 1 or o.dtype.kind not in "iu":
+                raise TypeError("group offsets must be a 1-D integer array of G + 1 entries")
+            o = np.ascontiguousarray(o.astype(np.int64, copy=False))
+            total = int(members.numel()) if torch is not None and isinstance(members, torch.Tensor) else int(np.asarray(members).size)
+            bad = bool((np.diff(o) < 0).any()) or int(o[0]) != 0 or int(o[-1]) != total
+            empty = bool((np.diff(o) == 0).any())
+            seg = torch.from_numpy(o).to(self._dev)
+        if not offs_dev or validate:
+            if bad:
+                raise ValueError("group offsets must be non-decreasing, start at 0 and end at the number of members")
+            if empty and op == "and":
+                raise ValueError("an empty group has no intersection")
+        G = int(seg.numel()) - 1
+        if G < 1:
+            raise ValueError("reduce needs at least one group")
+        if members is None:
+            raise TypeError("members must be an integer array or tensor")
+        _, rows = self._rows(members, validate, "members")
+        out = BloomFilterBank(G, self._est_elements, self._fpr, hash_function=self._hash_arg, device=self._device)
+        bits = torch.empty(G, dtype=torch.int64, device=self._dev)
+        N.check(N.lib().psk_bank_reduce(self._table.data_ptr(), self._num_filters, self._num_bits, seg.data_ptr(), self._addr(rows) or None, G,
+                                        1 if op == "and" else 0, out._table.data_ptr(), bits.data_ptr(), self._device, self._stream))
+        out._els = torch.from_numpy(self._estimates(bits.cpu().numpy())).to(self._dev)
+        return out
 
     # ------------------------------------------------------------------ single filters
     def filter(self, f) -> BloomFilter:

@@ -6,6 +6,8 @@
 //                                   the image's non-zero words into the table once (pass 2 of the Bloom step without the pass 1)
 //   psk_bank_slices / psk_bank_match  the bank transposed (slice row p = bit p of every filter) and "which filters may hold this key": the AND of
 //                                   the key's k slice rows, as a mask, a count or a list of filter ids
+//   psk_bank_popcount / psk_bank_overlap / psk_bank_reduce  the filters as sets: bits per row, popcount(a AND b) for all pairs (a tiled GEMM over
+//                                   (AND, popcount-add)), and the OR / AND of groups of rows stored as a new table
 #include "psk_stage.hpp"
 
 namespace {
@@ -312,6 +314,229 @@ __global__ __launch_bounds__(kBlock) void k_bank_match(Src src, const uint4 *sli
     }
 }
 
+// ---------------------------------------------------------------- the filters as sets (include/psk.h "bank statistics")
+// Rows are read whole, 16 bytes a lane: the pad bits of a row are never set, so a popcount over the padded row is the filter's bit count.
+__device__ __forceinline__ uint32_t popc4(uint4 v) { return __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w); }
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+    for (uint32_t o = 1; o < 64; o <<= 1) v += (uint32_t)__shfl_xor((int)v, (int)o);
+    return v;
+}
+
+// sum over the workgroup, in every thread; `red` = 4 words of LDS.  Two barriers: the caller may call it again at once.
+__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *red)
+{
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = red[0] + red[1] + red[2] + red[3];
+    __syncthreads();
+    return v;
+}
+
+// k_bank_popcount: WAVE: a wave per row, four rows per workgroup (rows of up to kBankPopWaveQuads 16-byte pieces); else a workgroup per row.
+// Row groups beyond the grid are walked with a stride.  Everything that decides a shuffle or a barrier is wave- / workgroup-uniform.
+constexpr uint32_t kBankPopWaveQuads = 256;  // 4 KiB: up to four loads per lane; wider rows take the whole workgroup
+template <bool WAVE>
+__global__ __launch_bounds__(kBlock) void k_bank_popcount(const uint4 *tab, uint64_t filters, uint32_t quads, const uint32_t *ids, uint64_t n, uint64_t *out)
+{
+    __shared__ uint32_t red[4];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t per = WAVE ? 4 : 1, me = WAVE ? lane : threadIdx.x, step = WAVE ? 64 : kBlock;
+    for (uint64_t base = (uint64_t)blockIdx.x * per; base < n; base += (uint64_t)gridDim.x * per) {
+        const uint64_t i = base + (WAVE ? wave : 0);
+        const uint64_t f = i < n ? (ids ? ids[i] : i) : filters;
+        uint32_t c = 0;
+        if (f < filters) {
+            const uint4 *row = tab + f * quads;  // (64-bit: filters * row_bytes may exceed 2^32)
+            for (uint32_t q = me; q < quads; q += step) c += popc4(row[q]);
+        }
+        if (WAVE) {
+            c = wave_sum(c);
+            if (lane == 0 && i < n) out[i] = c;
+        } else {
+            c = block_sum(c, red);
+            if (threadIdx.x == 0) out[i] = c;
+        }
+    }
+}
+
+// k_bank_overlap: out[i][j] = popcount(row a_i AND row b_j): a GEMM over the (AND, popcount-add) semiring.  A workgroup owns a T x T tile of
+// outputs, thread (ty, tx) = (tid >> 4, tid & 15) the 4 x 4 block at (4 ty, 4 tx).  The rows are walked in chunks of C words.  A chunk of the T
+// a-rows and of the T b-rows is loaded 16 bytes a lane -- four lanes read 64 contiguous bytes of one row, row pointers resolved through the id
+// lists -- and parked in LDS TRANSPOSED: word w of row r at [w][r], so that a thread's four rows at one word are ONE ds_read_b128.  The stride
+// of [w] is T + 4 words (a multiple of 4: the 16-byte reads stay aligned): the four ds_write_b32 of a lane fall on banks
+// (16 (quad & 1) + 4 j + row) mod 32 -- inside a 32-lane half (8 rows x 4 quads) 16 different banks, two lanes each, which a ds_write_b32 takes
+// at no extra cost; without the pad all four quads of a row would meet on ONE bank.  The reads: the a-side has 4 addresses per wave (broadcast),
+// the b-side 16 consecutive 16-byte pieces.  Per word and thread: 2 ds_read_b128 (8 dwords) feed 16 v_and_b32 + 16 v_bcnt_u32_b32.
+// A chunk's global loads are issued before the chunk in LDS is computed and land in registers under it.
+// Edges: a row beyond na / nb (a tile that hangs over) or an id beyond its table loads zeros; a chunk beyond the row's end loads zeros and the
+// inner loop stops at the row's last word; only outputs inside [na, nb) are stored.  Tiles are linearised on x and walked with a stride.
+// Few tiles of long rows (two filters of 2^31 bits are ONE tile) are cut along the rows: `splits` workgroups per tile take split_words words
+// each and add their counts into the zeroed output with atomics.
+// SYM (same table, same ids, na == nb): only tiles with tj >= ti exist (t = tj (tj + 1) / 2 + ti); each is stored at (ti, tj) and, off the
+// diagonal, transposed at (tj, ti).
+constexpr uint32_t kBankOvlT = 64, kBankOvlC = 32, kBankOvlStride = kBankOvlT + 4;
+constexpr uint32_t kBankOvlSplitChunks = 16;  // a part of a row, where rows are cut, is at least this many chunks
+constexpr uint32_t kBankOvlLoads = kBankOvlT * (kBankOvlC / 4) / kBlock;  // 16-byte loads per thread, chunk and side: 2
+static_assert(kBankOvlT == 64 && kBlock == 256 && kBankOvlC % 16 == 0, "the thread layout of k_bank_overlap");
+
+template <bool SYM>
+__global__ __launch_bounds__(kBlock) void k_bank_overlap(const uint4 *ta, uint64_t filters_a, const uint32_t *a_ids, uint64_t na, const uint4 *tb, uint64_t filters_b,
+                                                         const uint32_t *b_ids, uint64_t nb, uint32_t quads, uint32_t *out, uint64_t tiles_j, uint64_t work, int vec,
+                                                         uint32_t splits, uint32_t split_words)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t la[kBankOvlC * kBankOvlStride], lb[kBankOvlC * kBankOvlStride];
+    const uint32_t tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const uint32_t lrow = threadIdx.x >> 2, lq = threadIdx.x & 3;  // the load: row lrow of the tile, 16-byte piece lq + 4 p of the chunk
+    for (uint64_t item = blockIdx.x; item < work; item += gridDim.x) {
+        const uint64_t t = item / splits;
+        const uint32_t w_lo = (uint32_t)(item % splits) * split_words;  // this workgroup's words of the rows: [w_lo, w_hi), whole chunks but for the row's end
+        const uint32_t w_hi = quads * 4 - w_lo < split_words ? quads * 4 : w_lo + split_words;
+        uint64_t ti, tj;
+        if (SYM) {
+            tj = (uint64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+            while (tj * (tj + 1) / 2 > t) --tj;
+            while ((tj + 1) * (tj + 2) / 2 <= t) ++tj;
+            ti = t - tj * (tj + 1) / 2;
+        } else {
+            ti = t / tiles_j, tj = t % tiles_j;
+        }
+        const uint64_t i0 = ti * kBankOvlT, j0 = tj * kBankOvlT;
+        const uint64_t ia = i0 + lrow, jb = j0 + lrow;
+        const uint64_t fa = ia < na ? (a_ids ? a_ids[ia] : ia) : filters_a;
+        const uint64_t fb = jb < nb ? (b_ids ? b_ids[jb] : jb) : filters_b;
+        const uint4 *ra = fa < filters_a ? ta + fa * quads : nullptr;  // (64-bit: filters * row_bytes may exceed 2^32)
+        const uint4 *rb = fb < filters_b ? tb + fb * quads : nullptr;
+        uint32_t acc[4][4] = {};
+        uint4 va[kBankOvlLoads], vb[kBankOvlLoads];
+        // step s: issue the loads of chunk s, compute chunk s - 1 from LDS under them, then park chunk s
+        for (uint32_t w0 = w_lo;; w0 += kBankOvlC) {
+            const bool more = w0 < w_hi;
+            if (more) {
+#pragma unroll
+                for (uint32_t p = 0; p < kBankOvlLoads; ++p) {
+                    const uint32_t q = (w0 >> 2) + lq + 4 * p;
+                    va[p] = vb[p] = make_uint4(0u, 0u, 0u, 0u);
+                    if (ra && q < quads) va[p] = ra[q];
+                    if (rb && q < quads) vb[p] = rb[q];
+                }
+            }
+            if (w0 != w_lo) {
+                const uint32_t left = w_hi - (w0 - kBankOvlC), cw = left < kBankOvlC ? left : kBankOvlC;  // (a multiple of 4)
+#pragma clang loop vectorize(disable) unroll(disable)
+                for (uint32_t w4 = 0; w4 < cw; w4 += 4)
+#pragma unroll
+                for (uint32_t w = w4; w < w4 + 4; ++w) {
+                    const uint4 a = *reinterpret_cast<const uint4 *>(la + w * kBankOvlStride + 4 * ty);
+                    const uint4 b = *reinterpret_cast<const uint4 *>(lb + w * kBankOvlStride + 4 * tx);
+                    acc[0][0] += __popc(a.x & b.x), acc[0][1] += __popc(a.x & b.y), acc[0][2] += __popc(a.x & b.z), acc[0][3] += __popc(a.x & b.w);
+                    acc[1][0] += __popc(a.y & b.x), acc[1][1] += __popc(a.y & b.y), acc[1][2] += __popc(a.y & b.z), acc[1][3] += __popc(a.y & b.w);
+                    acc[2][0] += __popc(a.z & b.x), acc[2][1] += __popc(a.z & b.y), acc[2][2] += __popc(a.z & b.z), acc[2][3] += __popc(a.z & b.w);
+                    acc[3][0] += __popc(a.w & b.x), acc[3][1] += __popc(a.w & b.y), acc[3][2] += __popc(a.w & b.z), acc[3][3] += __popc(a.w & b.w);
+                }
+            }
+            if (!more) break;
+            __syncthreads();  // every thread is done reading the chunk before (the tile before)
+#pragma unroll
+            for (uint32_t p = 0; p < kBankOvlLoads; ++p) {
+                uint32_t *da = la + (4 * (lq + 4 * p)) * kBankOvlStride + lrow, *db = lb + (4 * (lq + 4 * p)) * kBankOvlStride + lrow;
+                da[0] = va[p].x, da[kBankOvlStride] = va[p].y, da[2 * kBankOvlStride] = va[p].z, da[3 * kBankOvlStride] = va[p].w;
+                db[0] = vb[p].x, db[kBankOvlStride] = vb[p].y, db[2 * kBankOvlStride] = vb[p].z, db[3 * kBankOvlStride] = vb[p].w;
+            }
+            __syncthreads();
+        }
+        const uint64_t oi = i0 + 4 * ty, oj = j0 + 4 * tx;
+        if (splits > 1) {  // (uniform) the parts of a pair's rows meet in the zeroed output through atomics
+#pragma unroll
+            for (uint32_t r = 0; r < 4; ++r)
+#pragma unroll
+                for (uint32_t c = 0; c < 4; ++c) {
+                    if (oi + r >= na || oj + c >= nb || !acc[r][c]) continue;
+                    atomicAdd(out + (oi + r) * nb + oj + c, acc[r][c]);
+                    if (SYM && ti != tj) atomicAdd(out + (oj + c) * nb + oi + r, acc[r][c]);
+                }
+            continue;
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < 4; ++r) {
+            if (oi + r >= na) continue;
+            uint32_t *o = out + (oi + r) * nb + oj;
+            if (vec && oj + 4 <= nb) {
+                *reinterpret_cast<uint4 *>(o) = make_uint4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+            } else {
+#pragma unroll
+                for (uint32_t c = 0; c < 4; ++c)
+                    if (oj + c < nb) o[c] = acc[r][c];
+            }
+        }
+        if (SYM && ti != tj) {  // (na == nb: the transposed block lies at rows oj .., columns oi ..)
+#pragma unroll
+            for (uint32_t c = 0; c < 4; ++c) {
+                if (oj + c >= nb) continue;
+                uint32_t *o = out + (oj + c) * nb + oi;
+                if (vec && oi + 4 <= na) {
+                    *reinterpret_cast<uint4 *>(o) = make_uint4(acc[0][c], acc[1][c], acc[2][c], acc[3][c]);
+                } else {
+#pragma unroll
+                    for (uint32_t r = 0; r < 4; ++r)
+                        if (oi + r < na) o[r] = acc[r][c];
+                }
+            }
+        }
+    }
+}
+
+// k_bank_reduce: a workgroup per (group, piece of kBlock 16-byte pieces of the row), linearised on x and walked with a stride.  A thread folds its
+// 16 bytes of the group's member rows in registers (four members' loads in flight), STORES the result and adds the piece's popcount to
+// bits[g]: a plain store where the row is one piece, an atomic on the zeroed counter else.  An empty group stores zeros under either op; a
+// member >= filters counts as an empty row.
+__global__ __launch_bounds__(kBlock) void k_bank_reduce(const uint4 *src, uint64_t filters, uint32_t quads, const uint64_t *seg, const uint32_t *members, uint64_t groups,
+                                                        int op_and, uint4 *dst, uint64_t *bits, uint32_t pieces, uint64_t work)
+{
+    __shared__ uint32_t red[4];
+    for (uint64_t t = blockIdx.x; t < work; t += gridDim.x) {
+        const uint64_t g = t / pieces;
+        const uint32_t q = (uint32_t)(t % pieces) * kBlock + threadIdx.x;
+        const uint64_t s0 = seg[g], s1 = seg[g + 1];
+        const bool on = q < quads;
+        const uint32_t init = op_and && s1 > s0 ? ~0u : 0u;
+        uint4 acc = make_uint4(init, init, init, init);
+        if (on) {
+            auto row = [&](uint64_t j) {
+                const uint64_t f = members[j];
+                return f < filters ? src[f * quads + q] : make_uint4(0u, 0u, 0u, 0u);
+            };
+            auto fold = [&](const uint4 &v) {
+                if (op_and) acc.x &= v.x, acc.y &= v.y, acc.z &= v.z, acc.w &= v.w;
+                else acc.x |= v.x, acc.y |= v.y, acc.z |= v.z, acc.w |= v.w;
+            };
+            uint64_t j = s0;
+            for (; j + 4 <= s1; j += 4) {
+                const uint4 v0 = row(j), v1 = row(j + 1), v2 = row(j + 2), v3 = row(j + 3);
+                fold(v0), fold(v1), fold(v2), fold(v3);
+            }
+            for (; j < s1; ++j) fold(row(j));
+            dst[g * quads + q] = acc;
+        }
+        if (bits) {  // (uniform)
+            const uint32_t c = block_sum(on ? popc4(acc) : 0u, red);
+            if (threadIdx.x == 0) {
+                if (pieces == 1) bits[g] = c;
+                else if (c) atomicAdd(reinterpret_cast<unsigned long long *>(bits + g), (unsigned long long)c);
+            }
+        }
+    }
+}
+
+int stats_check_table(const void *table_dev, uint64_t filters, uint64_t m_bits)
+{
+    if (!table_dev) return fail(PSK_EINVAL, "NULL table pointer");
+    if ((uintptr_t)table_dev & 15) return fail(PSK_EINVAL, "a bank table must be 16-byte aligned");
+    return slice_check_geometry(filters, m_bits);
+}
+
 }  // namespace
 
 extern "C" uint64_t psk_bank_row_bytes(uint64_t m_bits) { return psk_bloom_table_bytes(m_bits); }
@@ -434,4 +659,88 @@ extern "C" int psk_bank_match(const void *slices_dev, uint64_t filters, uint64_t
             });
         }));
     return finish(where, nullptr, st);
+}
+
+// ---------------------------------------------------------------- bank statistics: bit counts, all-pairs overlap, row folds
+extern "C" int psk_bank_popcount(const void *table_dev, uint64_t filters, uint64_t m_bits, const uint32_t *ids_dev, uint64_t n, uint64_t *out_dev, int device,
+                                 void *stream)
+{
+    PSK_TRY(stats_check_table(table_dev, filters, m_bits));
+    if (!ids_dev && n != filters)
+        return fail(PSK_EINVAL, "without ids every row is counted: n must be the number of filters (%llu), not %llu", (unsigned long long)filters, (unsigned long long)n);
+    if (n == 0) return PSK_OK;
+    if (!out_dev) return fail(PSK_EINVAL, "out_dev is NULL");
+    const uint64_t quads = psk_bank_row_bytes(m_bits) / 16;
+    PSK_USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    if (quads <= kBankPopWaveQuads) {
+        const uint64_t wgs = (n + 3) / 4;
+        hipLaunchKernelGGL(k_bank_popcount<true>, dim3((unsigned)(wgs < kBankGridCap ? wgs : kBankGridCap)), dim3(kBlock), 0, st, (const uint4 *)table_dev, filters,
+                           (uint32_t)quads, ids_dev, n, out_dev);
+    } else {
+        hipLaunchKernelGGL(k_bank_popcount<false>, dim3((unsigned)(n < kBankGridCap ? n : kBankGridCap)), dim3(kBlock), 0, st, (const uint4 *)table_dev, filters,
+                           (uint32_t)quads, ids_dev, n, out_dev);
+    }
+    HIP_TRY(hipGetLastError());
+    return PSK_OK;
+}
+
+extern "C" int psk_bank_overlap(const void *table_a_dev, uint64_t filters_a, const uint32_t *a_ids_dev, uint64_t na, const void *table_b_dev, uint64_t filters_b,
+                                const uint32_t *b_ids_dev, uint64_t nb, uint64_t m_bits, uint32_t *out_dev, int device, void *stream)
+{
+    PSK_TRY(stats_check_table(table_a_dev, filters_a, m_bits));
+    PSK_TRY(stats_check_table(table_b_dev, filters_b, m_bits));
+    if (!a_ids_dev && na > filters_a)
+        return fail(PSK_EINVAL, "without a_ids rows 0 .. na - 1 are taken: na = %llu exceeds the table's %llu filters", (unsigned long long)na, (unsigned long long)filters_a);
+    if (!b_ids_dev && nb > filters_b)
+        return fail(PSK_EINVAL, "without b_ids rows 0 .. nb - 1 are taken: nb = %llu exceeds the table's %llu filters", (unsigned long long)nb, (unsigned long long)filters_b);
+    if ((na >> 32) || (nb >> 32)) return fail(PSK_EINVAL, "an overlap call takes fewer than 2^32 rows a side; %llu x %llu were passed", (unsigned long long)na, (unsigned long long)nb);
+    if (na == 0 || nb == 0) return PSK_OK;
+    if (!out_dev) return fail(PSK_EINVAL, "out_dev is NULL");
+    const uint64_t quads = psk_bank_row_bytes(m_bits) / 16;
+    const uint64_t tiles_i = (na + kBankOvlT - 1) / kBankOvlT, tiles_j = (nb + kBankOvlT - 1) / kBankOvlT;
+    const bool sym = table_a_dev == table_b_dev && a_ids_dev == b_ids_dev && na == nb && filters_a == filters_b;
+    const uint64_t tiles = sym ? tiles_i * (tiles_i + 1) / 2 : tiles_i * tiles_j;
+    const int vec = (nb & 3) == 0 && ((uintptr_t)out_dev & 15) == 0;  // 16-byte stores of a thread's four columns
+    // fewer tiles than the grid holds: cut the rows into parts of at least kBankOvlSplitChunks chunks until the grid is full
+    const uint64_t chunks = (quads * 4 + kBankOvlC - 1) / kBankOvlC;
+    uint64_t splits = chunks / kBankOvlSplitChunks < kBankGridCap / tiles ? chunks / kBankOvlSplitChunks : kBankGridCap / tiles;
+    if (splits < 1) splits = 1;
+    const uint64_t per = (chunks + splits - 1) / splits;
+    splits = (chunks + per - 1) / per;  // (no empty part)
+    const uint64_t work = tiles * splits;
+    const dim3 grid((unsigned)(work < kBankGridCap ? work : kBankGridCap));
+    PSK_USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    if (splits > 1) HIP_TRY(hipMemsetAsync(out_dev, 0, na * nb * sizeof(uint32_t), st));
+    if (sym)
+        hipLaunchKernelGGL(k_bank_overlap<true>, grid, dim3(kBlock), 0, st, (const uint4 *)table_a_dev, filters_a, a_ids_dev, na, (const uint4 *)table_b_dev, filters_b,
+                           b_ids_dev, nb, (uint32_t)quads, out_dev, tiles_j, work, vec, (uint32_t)splits, (uint32_t)(per * kBankOvlC));
+    else
+        hipLaunchKernelGGL(k_bank_overlap<false>, grid, dim3(kBlock), 0, st, (const uint4 *)table_a_dev, filters_a, a_ids_dev, na, (const uint4 *)table_b_dev, filters_b,
+                           b_ids_dev, nb, (uint32_t)quads, out_dev, tiles_j, work, vec, (uint32_t)splits, (uint32_t)(per * kBankOvlC));
+    HIP_TRY(hipGetLastError());
+    return PSK_OK;
+}
+
+extern "C" int psk_bank_reduce(const void *src_dev, uint64_t filters, uint64_t m_bits, const uint64_t *seg_dev, const uint32_t *members_dev, uint64_t groups, int op,
+                               void *dst_dev, uint64_t *bits_dev, int device, void *stream)
+{
+    PSK_TRY(stats_check_table(src_dev, filters, m_bits));
+    if (op != 0 && op != 1) return fail(PSK_EINVAL, "op must be 0 (OR) or 1 (AND); %d was passed", op);
+    if (groups >> 32) return fail(PSK_EINVAL, "a reduce call takes fewer than 2^32 groups; %llu were passed", (unsigned long long)groups);
+    if (groups == 0) return PSK_OK;
+    if (!dst_dev || ((uintptr_t)dst_dev & 15)) return fail(PSK_EINVAL, "dst_dev must be a 16-byte aligned device pointer");
+    if (!seg_dev) return fail(PSK_EINVAL, "seg_dev is NULL");
+    const uint64_t row_bytes = psk_bank_row_bytes(m_bits), quads = row_bytes / 16;
+    const uintptr_t s0 = (uintptr_t)src_dev, s1 = s0 + filters * row_bytes, d0 = (uintptr_t)dst_dev, d1 = d0 + groups * row_bytes;
+    if (d0 < s1 && s0 < d1) return fail(PSK_EINVAL, "dst overlaps src: a fold is stored, never done in place");
+    const uint64_t pieces = (quads + kBlock - 1) / kBlock, work = groups * pieces;
+    PSK_USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    if (bits_dev && pieces > 1) HIP_TRY(hipMemsetAsync(bits_dev, 0, groups * sizeof(uint64_t), st));
+    hipLaunchKernelGGL(k_bank_reduce, dim3((unsigned)(work < kBankGridCap ? work : kBankGridCap)), dim3(kBlock), 0, st, (const uint4 *)src_dev, filters, (uint32_t)quads,
+                       seg_dev, members_dev, groups, op, (uint4 *)dst_dev, bits_dev, (uint32_t)pieces, work);
+    HIP_TRY(hipGetLastError());
+    return PSK_OK;
 }
