@@ -454,6 +454,26 @@ int psk_bank_match(const void *slices_dev, uint64_t filters, uint64_t m_bits, ui
                    uint64_t n, uint32_t key_len, int where, uint32_t *mask_dev, uint32_t *count_dev, const uint64_t *out_offsets_dev,
                    uint32_t *ids_dev, int device, void *stream);
 
+/* Scoring a query against every filter (the threshold queries of BIGSI / COBS).  A query is a set of keys: query q is keys
+ * [query_offsets_dev[q], query_offsets_dev[q + 1]) of the batch (uint64[queries + 1], device memory, non-decreasing from 0 to n; not checked --
+ * whatever it holds, no key at or beyond n is read).  The slice image and the keys are those of psk_bank_match; the per-key mask never leaves the CU.
+ *   score   scores_dev[q * filters + f] (uint32[queries][filters] in device memory whatever `where` says: the row stride is `filters` words, the
+ *           image's pad columns have no column, nothing is written beyond queries * filters words) = the number of keys i of query q whose k bits
+ *           are all set in filter f: the sum of psk_bank_check's answers for (i, f), a repeated key counted each time.  A score is below 2^31.
+ *           split (1 .. 65535): workgroups per query, each taking a contiguous part of its keys; with split > 1 the call zeroes scores_dev on
+ *           `stream` and the parts add into it.  The result is the same for every split.  An empty query's row is zeros; queries == 0 launches
+ *           nothing; n == 0 writes zero rows.  k <= 64 as for match.  Keys follow `where` (a PSK_HOST call returns when the kernel has read them).
+ *           Element offsets are 64-bit: queries * filters may pass 2^32.  Enqueue only.  (DESIGN.md 3.13 "Scoring a query")
+ *   score_select  over finished scores: count_dev[q] = the number of filters f with scores[q][f] >= thresholds_dev[q] (uint32[queries], device,
+ *           every value >= 1); ids_dev[out_offsets_dev[q] ...] = those filters, ascending, and hit_scores_dev[out_offsets_dev[q] ...] = their
+ *           scores beside them (out_offsets_dev = uint64[queries], the exclusive prefix sums of a counts call).  Each output may be NULL, at least
+ *           one must be given; ids_dev and out_offsets_dev go together; hit_scores_dev needs ids_dev, ids_dev may come without it. */
+int psk_bank_score(const void *slices_dev, uint64_t filters, uint64_t m_bits, uint32_t k, int layout, const void *data, const uint64_t *offsets,
+                   uint64_t n, uint32_t key_len, int where, const uint64_t *query_offsets_dev, uint64_t queries, uint32_t split,
+                   uint32_t *scores_dev, int device, void *stream);
+int psk_bank_score_select(const uint32_t *scores_dev, uint64_t queries, uint64_t filters, const uint32_t *thresholds_dev, uint32_t *count_dev,
+                          const uint64_t *out_offsets_dev, uint32_t *ids_dev, uint32_t *hit_scores_dev, int device, void *stream);
+
 /* Bank statistics: the filters of a bank as sets -- what the reference answers per object, for every row (pair, group) in one launch.
  * No handle: tables, id lists, seg / members and outputs are device memory owned by the caller; tables and dst are 16-byte aligned.  Enqueue
  * only, on `stream`.  Rows are read whole (psk_bank_row_bytes): the pad bits of a row are never set.  An id at or beyond its table counts as

@@ -91,6 +91,8 @@ PROTOTYPES = {
     "psk_bank_slice_row_bytes": (_u64, [_u64]),
     "psk_bank_slices": (_int, [_vp, _u64, _u64, _vp, _u64, _u64, _int, _vp]),
     "psk_bank_match": (_int, [_vp, _u64, _u64, _u32, *_KEYS, _int, _vp, _vp, _vp, _vp, _int, _vp]),
+    "psk_bank_score": (_int, [_vp, _u64, _u64, _u32, *_KEYS, _int, _vp, _u64, _u32, _vp, _int, _vp]),
+    "psk_bank_score_select": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "psk_bank_popcount": (_int, [_vp, _u64, _u64, _vp, _u64, _vp, _int, _vp]),
     "psk_bank_overlap": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _vp, _int, _vp]),
     "psk_bank_reduce": (_int, [_vp, _u64, _u64, _vp, _vp, _u64, _int, _vp, _vp, _int, _vp]),

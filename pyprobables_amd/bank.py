@@ -11,6 +11,8 @@ an LDS image of the row and ORs the image into the table once (``psk_bank_build`
 "Which filters may hold this key?" is answered from a second copy of the table, the *slice image*: the bank transposed (``psk_bank_slices``),
 row ``p`` holding bit ``p`` of every filter.  All filters share the geometry and the hash family, so the answer for one key is the AND of
 its k slice rows (``psk_bank_match``).  The image is allocated on the first match and refreshed lazily: updates only mark it stale.
+A *query* -- a set of keys: the k-mers of a read, the terms of a document -- is scored against every filter by the same row-AND
+(``psk_bank_score``: per filter, how many of the query's keys it may hold), and ``psk_bank_score_select`` keeps the filters at a threshold.
 
 The filters as sets are read from the table alone: ``bits_set`` / ``estimate_elements`` (``psk_bank_popcount``), ``overlap`` /
 ``jaccard`` for all pairs of two lists of filters (``psk_bank_overlap``: a tiled GEMM over AND and popcount), and ``reduce``, the union or
@@ -66,6 +68,40 @@ def group_ids(ids, num_filters: int):
     return perm, seg
 
 
+def score_thresholds(lengths, threshold) -> np.ndarray:
+    """the per-query thresholds of ``score_many``: uint32[queries] for queries of ``lengths`` keys.  An ``int >= 1`` holds for every query; an
+    integer array of ``queries`` values >= 1 gives each query its own; a ``float`` in (0, 1] is the COBS-style fraction of the query's keys,
+    ``t_q = max(1, ceil(float64(threshold) * len_q))``.  Anything else raises ``TypeError`` / ``ValueError``.  Pure numpy: no GPU."""
+    lengths = np.asarray(lengths)
+    if lengths.ndim != 1 or (lengths.size and lengths.dtype.kind not in "iu"):
+        raise TypeError("lengths must be a 1-D integer array")
+    if isinstance(threshold, (bool, np.bool_)):
+        raise TypeError("threshold must be an int, an integer array or a float, not a bool")
+    if isinstance(threshold, (int, np.integer)):
+        if not 1 <= int(threshold) < 2**32:
+            raise ValueError("an integer threshold must lie in [1, 2^32)")
+        return np.full(lengths.size, int(threshold), dtype=np.uint32)
+    if isinstance(threshold, (float, np.floating)):
+        if not 0.0 < float(threshold) <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError("a fractional threshold must lie in (0, 1]")
+        t = np.ceil(np.float64(threshold) * lengths.astype(np.float64))
+        return np.maximum(t, 1.0).astype(np.uint32)
+    if torch is not None and isinstance(threshold, torch.Tensor):
+        threshold = threshold.cpu().numpy()
+    if isinstance(threshold, (str, bytes)) or not isinstance(threshold, (np.ndarray, list, tuple)):
+        raise TypeError("threshold must be an int, an integer array or a float")
+    a = np.asarray(threshold)
+    if a.size == 0 and a.ndim == 1:  # (an empty list has no integer dtype of its own)
+        a = a.astype(np.int64)
+    if a.dtype.kind not in "iu" or a.ndim != 1:
+        raise TypeError("per-query thresholds must be a 1-D integer array")
+    if a.size != lengths.size:
+        raise ValueError(f"per-query thresholds: {a.size} values for {lengths.size} queries")
+    if a.size and (int(a.min()) < 1 or int(a.max()) >= 2**32):
+        raise ValueError("per-query thresholds must lie in [1, 2^32)")
+    return a.astype(np.uint32)
+
+
 def _slice_batch(b: KeyBatch, lo: int, hi: int) -> KeyBatch:
     """keys [lo, hi) of a batch, without copying the keys"""
     if lo == 0 and hi == b.n:
@@ -113,6 +149,7 @@ class BloomFilterBank(DeviceResident):
         self._route = 0            # psk_bank_build's route: 0 auto per workgroup, 1 LDS image, 2 global atomics
         self._last_path = None     # "direct" / "grouped": the way the last update took
         self._split = None         # workgroups per filter; None: 1, or ceil(2 * CUs / num_filters) for a bank of fewer than 2 * CUs filters
+        self._score_split = None   # workgroups per query of a score call; None: 1, or ceil(2 * CUs / queries) for fewer than 2 * CUs queries
         self._slice_row_bytes = int(L.psk_bank_slice_row_bytes(self._num_filters))
         self._slices = None        # the slice image (match_many), allocated on the first match
         self._stale_all = True     # the image lags behind the table: everywhere / in these 32-filter column groups
@@ -184,27 +221,29 @@ class BloomFilterBank(DeviceResident):
             raise ValueError(f"filter ids must lie in [0, {self._num_filters})")
         return torch.from_numpy(np.ascontiguousarray(a)).to(self._dev) if where == N.DEVICE else a
 
-    def _offsets(self, offs, n: int, where: int, validate: bool):
-        """filter_offsets[num_filters + 1] -> as _ids: where the keys are, checked (non-decreasing, from 0 to n)"""
+    def _offsets(self, offs, n: int, where: int, validate: bool, count=None, what: str = "filter_offsets"):
+        """offsets[count + 1] (filter_offsets: count = num_filters; query_offsets: any count >= 0, None) -> as _ids: where the keys are, checked
+        (non-decreasing, from 0 to n)"""
         is_dev = torch is not None and isinstance(offs, torch.Tensor) and offs.is_cuda
-        F = self._num_filters
+        want = f"{count + 1} integers" if count is not None else "a 1-D integer array of queries + 1 entries"
+        size = int(offs.numel()) if torch is not None and isinstance(offs, torch.Tensor) else None
         if is_dev:
-            if offs.dim() != 1 or offs.numel() != F + 1 or offs.is_floating_point() or offs.dtype == torch.bool:
-                raise TypeError(f"filter_offsets must be {F + 1} integers")
+            if offs.dim() != 1 or size < 1 or (count is not None and size != count + 1) or offs.is_floating_point() or offs.dtype == torch.bool:
+                raise TypeError(f"{what} must be {want}")
             if offs.device.index != self._device:
-                raise ValueError(f"filter_offsets live on cuda:{offs.device.index}, the bank on cuda:{self._device}")
+                raise ValueError(f"{what} live on cuda:{offs.device.index}, the bank on cuda:{self._device}")
             o = offs.to(torch.int64).contiguous()
             if validate:  # one reduction, one synchronisation
                 bad = (o[1:] < o[:-1]).any() | (o[0] != 0) | (o[-1] != n)
                 if bool(bad.item()):
-                    raise ValueError("filter_offsets must be non-decreasing, start at 0 and end at the number of keys")
+                    raise ValueError(f"{what} must be non-decreasing, start at 0 and end at the number of keys")
             return o if where == N.DEVICE else o.cpu().numpy()
         a = offs.numpy() if torch is not None and isinstance(offs, torch.Tensor) else np.asarray(offs)
-        if a.ndim != 1 or a.size != F + 1 or a.dtype.kind not in "iu":
-            raise TypeError(f"filter_offsets must be {F + 1} integers")
+        if a.ndim != 1 or a.size < 1 or (count is not None and a.size != count + 1) or a.dtype.kind not in "iu":
+            raise TypeError(f"{what} must be {want}")
         a = np.ascontiguousarray(a.astype(np.int64, copy=False))
         if (np.diff(a) < 0).any() or int(a[0]) != 0 or int(a[-1]) != n:
-            raise ValueError("filter_offsets must be non-decreasing, start at 0 and end at the number of keys")
+            raise ValueError(f"{what} must be non-decreasing, start at 0 and end at the number of keys")
         return torch.from_numpy(a).to(self._dev) if where == N.DEVICE else a
 
     @staticmethod
@@ -260,7 +299,7 @@ class BloomFilterBank(DeviceResident):
             raise ValueError(f"unknown _add_policy {self._add_policy!r}")
         F = self._num_filters
         if filter_offsets is not None:
-            offs = self._offsets(filter_offsets, b.n, b.where, validate)
+            offs = self._offsets(filter_offsets, b.n, b.where, validate, self._num_filters)
             if b.n == 0:
                 return
             if b.where == N.DEVICE and self._add_policy != "direct":  # keys that arrive grouped: the build kernel as they lie
@@ -366,16 +405,20 @@ class BloomFilterBank(DeviceResident):
         self._stale_all = False
         self._stale_groups.clear()
 
+    def _image_ready(self, b: KeyBatch, what: str) -> None:
+        """in front of every call that reads the slice image (match, score): the cap on k, the batch size, and the lazy refresh"""
+        if self._number_hashes > BANK_MATCH_MAX_HASHES:
+            raise NotSupportedError(f"{what}_many takes filters of at most {BANK_MATCH_MAX_HASHES} hashes (this bank has {self._number_hashes}): "
+                                    "use check_many(keys, ids) with the filter ids spelled out")
+        if b.n > self._CHUNK:
+            raise ValueError(f"a {what} call takes fewer than 2^32 keys")
+        if self._stale_all or self._stale_groups or self._slices is None:
+            self.refresh_slices()
+
     def _match_batch(self, b: KeyBatch, form: str):
         if form not in ("mask", "count", "ids"):
             raise ValueError(f"form must be 'mask', 'count' or 'ids', not {form!r}")
-        if self._number_hashes > BANK_MATCH_MAX_HASHES:
-            raise NotSupportedError(f"match_many takes filters of at most {BANK_MATCH_MAX_HASHES} hashes (this bank has {self._number_hashes}): "
-                                    "use check_many(keys, ids) with the filter ids spelled out")
-        if b.n > self._CHUNK:
-            raise ValueError("a match call takes fewer than 2^32 keys")
-        if self._stale_all or self._stale_groups or self._slices is None:
-            self.refresh_slices()
+        self._image_ready(b, "match")
         L, n, words = N.lib(), b.n, self._slice_row_bytes // 4
         host = b.where == N.HOST
 
@@ -417,6 +460,68 @@ class BloomFilterBank(DeviceResident):
             raise TypeError("match takes one key; use match_many for a batch")
         _, ids = self._match_batch(b, "ids")
         return [int(f) for f in (ids if isinstance(ids, np.ndarray) else ids.cpu().numpy())]
+
+    # ------------------------------------------------------------------ scoring a query: how many of its keys each filter may hold
+    def score_split_for(self, queries: int) -> int:
+        """workgroups per query of a score call: 1 unless there are fewer than twice as many queries as the device has CUs (the rule of
+        :meth:`split_for`; ``_score_split`` overrides it).  Not measured: no run has compared splits yet."""
+        if self._score_split is not None:
+            return int(self._score_split)
+        return 1 if queries == 0 or queries >= 2 * self._cus else -(-2 * self._cus // queries)
+
+    def _score_batch(self, b: KeyBatch, query_offsets, threshold, validate: bool):
+        qo = self._offsets(query_offsets, b.n, N.DEVICE, validate, None, "query_offsets")
+        L, F, Q, host = N.lib(), self._num_filters, int(qo.numel()) - 1, b.where == N.HOST
+        thr = None
+        if threshold is not None:  # (offsets and thresholds are refused before the image is touched)
+            fraction = isinstance(threshold, (float, np.floating))
+            lengths = (qo[1:] - qo[:-1]).cpu().numpy() if fraction else np.zeros(Q, dtype=np.int64)
+            thr = torch.from_numpy(score_thresholds(lengths, threshold).view(np.int32)).to(self._dev)
+        self._image_ready(b, "score")
+        scores = torch.empty((Q, F), dtype=torch.int32, device=self._dev)
+        if Q:
+            N.check(L.psk_bank_score(self._slices.data_ptr(), F, self._num_bits, self._number_hashes, *b.args(), b.where, qo.data_ptr(), Q,
+                                     self.score_split_for(Q), scores.data_ptr(), self._device, self._stream))
+        if thr is None:
+            return scores.cpu().numpy() if host else scores
+
+        def select(count=None, offs=None, ids=None, hit=None):
+            if Q:
+                N.check(L.psk_bank_score_select(scores.data_ptr(), Q, F, thr.data_ptr(), *(None if t is None else t.data_ptr() for t in (count, offs, ids, hit)),
+                                                self._device, self._stream))
+
+        count = torch.empty(Q, dtype=torch.int32, device=self._dev)
+        select(count=count)
+        offsets = torch.zeros(Q + 1, dtype=torch.int64, device=self._dev)
+        torch.cumsum(count, 0, out=offsets[1:])
+        total = int(offsets[-1].item())
+        ids, hit = (torch.empty(total, dtype=torch.int32, device=self._dev) for _ in range(2))
+        if total:
+            select(offs=offsets, ids=ids, hit=hit)
+        return tuple(t.cpu().numpy() for t in (offsets, ids, hit)) if host else (offsets, ids, hit)
+
+    def score_many(self, keys, query_offsets, threshold=None, validate: bool = True):
+        """whole queries against every filter: query q is ``keys[query_offsets[q]:query_offsets[q + 1]]`` (``query_offsets``: ``queries + 1``
+        integers, host or device, non-decreasing from 0 to n; host arrays are always checked, device tensors with one reduction unless
+        ``validate=False``), and ``score[q, f]`` is the number of its keys that filter f may hold -- the sum over the query of
+        ``key in filter f`` (bloom.py:261-272), a repeated key counted each time.  The per-key mask of :meth:`match_many` is never written.
+        ``threshold=None``: int32 ``[queries, num_filters]``.  With a threshold (see :func:`score_thresholds`: an int, one int per query, or a
+        fraction of each query's length): ``(offsets int64[queries + 1], ids int32[total], scores int32[total])``, the filters of query q with
+        ``score >= t_q`` are ``ids[offsets[q]:offsets[q + 1]]``, ascending, their scores beside them.  Device keys give tensors on the device,
+        host keys numpy arrays.  Nothing here changes the table or marks the slice image stale."""
+        return self._score_batch(self._batch(keys), query_offsets, threshold, validate)
+
+    def score_alt_many(self, hashes, query_offsets, threshold=None, validate: bool = True):
+        """:meth:`score_many` for pre-computed hashes: (n, >= k) uint64"""
+        return self._score_batch(self._same_device(pack_hashes(hashes, self._number_hashes)), query_offsets, threshold, validate)
+
+    def score(self, keys, threshold=None):
+        """one query made of all the keys: numpy int32[num_filters], or with a threshold ``(ids, scores)`` as numpy arrays"""
+        b = self._batch(keys)
+        r = self._score_batch(b, np.array([0, b.n], dtype=np.int64), threshold, True)
+        if threshold is None:
+            return (r if isinstance(r, np.ndarray) else r.cpu().numpy())[0]
+        return tuple(x if isinstance(x, np.ndarray) else x.cpu().numpy() for x in r[1:])
 
     # ------------------------------------------------------------------ the filters as sets: bit counts, estimates, overlap, folds
     def _rows(self, ids, validate: bool, what: str = "ids"):

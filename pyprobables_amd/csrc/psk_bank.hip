@@ -6,6 +6,8 @@
 //                                   the image's non-zero words into the table once (pass 2 of the Bloom step without the pass 1)
 //   psk_bank_slices / psk_bank_match  the bank transposed (slice row p = bit p of every filter) and "which filters may hold this key": the AND of
 //                                   the key's k slice rows, as a mask, a count or a list of filter ids
+//   psk_bank_score / psk_bank_score_select  a query = a set of keys: per filter, how many of the query's keys it may hold (the same row-AND, added
+//                                   into bit-plane counters in registers), and the filters of each query that reach a threshold
 //   psk_bank_popcount / psk_bank_overlap / psk_bank_reduce  the filters as sets: bits per row, popcount(a AND b) for all pairs (a tiled GEMM over
 //                                   (AND, popcount-add)), and the OR / AND of groups of rows stored as a new table
 #include "psk_stage.hpp"
@@ -238,6 +240,27 @@ __global__ __launch_bounds__(kBlock) void k_bank_slices(const uint32_t *tab, uin
     }
 }
 
+// The AND of a key's k slice rows at one 16-byte column piece: `col` = the piece in slice row 0, pp[j * stride] = bit position j of the key (LDS),
+// rows `quads` pieces apart (64-bit: position * row bytes may pass 2^32).  k independent loads, four in flight.  Shared by k_bank_match and k_bank_score.
+__device__ __forceinline__ uint4 bank_row_and(const uint4 *col, const uint32_t *pp, uint32_t stride, uint32_t k, uint32_t quads)
+{
+    uint4 acc = make_uint4(~0u, ~0u, ~0u, ~0u);
+    uint32_t j = 0;
+    for (; j + 4 <= k; j += 4) {
+        const uint32_t p0 = pp[j * stride], p1 = pp[(j + 1) * stride], p2 = pp[(j + 2) * stride], p3 = pp[(j + 3) * stride];
+        const uint4 a0 = col[(uint64_t)p0 * quads], a1 = col[(uint64_t)p1 * quads], a2 = col[(uint64_t)p2 * quads], a3 = col[(uint64_t)p3 * quads];
+        acc.x &= a0.x & a1.x & a2.x & a3.x;
+        acc.y &= a0.y & a1.y & a2.y & a3.y;
+        acc.z &= a0.z & a1.z & a2.z & a3.z;
+        acc.w &= a0.w & a1.w & a2.w & a3.w;
+    }
+    for (; j < k; ++j) {
+        const uint4 a = col[(uint64_t)pp[j * stride] * quads];
+        acc.x &= a.x, acc.y &= a.y, acc.z &= a.z, acc.w &= a.w;
+    }
+    return acc;
+}
+
 // k_bank_match: a workgroup takes 256 keys a round.  Phase A, lane = key: the k bit positions go to LDS as pos[j][thread].  Phase B, per wave over
 // its 64 keys: G lanes per key (G = 2^lgG covers the row's 16-byte pieces, at most 64; wider rows are walked in 1 KiB chunks), each lane ANDs the k
 // 16-byte pieces of its column block -- k independent loads, four in flight -- and stores the mask piece; popcounts are reduced (count) or scanned
@@ -269,21 +292,7 @@ __global__ __launch_bounds__(kBlock) void k_bank_match(Src src, const uint4 *sli
                 const bool on = live && qd < quads;
                 uint4 acc = make_uint4(0u, 0u, 0u, 0u);
                 if (on) {
-                    acc = make_uint4(~0u, ~0u, ~0u, ~0u);
-                    const uint4 *col = slices + qd;
-                    uint32_t j = 0;
-                    for (; j + 4 <= k; j += 4) {
-                        const uint32_t p0 = pp[j * kBlock], p1 = pp[(j + 1) * kBlock], p2 = pp[(j + 2) * kBlock], p3 = pp[(j + 3) * kBlock];
-                        const uint4 a0 = col[(uint64_t)p0 * quads], a1 = col[(uint64_t)p1 * quads], a2 = col[(uint64_t)p2 * quads], a3 = col[(uint64_t)p3 * quads];
-                        acc.x &= a0.x & a1.x & a2.x & a3.x;
-                        acc.y &= a0.y & a1.y & a2.y & a3.y;
-                        acc.z &= a0.z & a1.z & a2.z & a3.z;
-                        acc.w &= a0.w & a1.w & a2.w & a3.w;
-                    }
-                    for (; j < k; ++j) {
-                        const uint4 a = col[(uint64_t)pp[j * kBlock] * quads];
-                        acc.x &= a.x, acc.y &= a.y, acc.z &= a.z, acc.w &= a.w;
-                    }
+                    acc = bank_row_and(slices + qd, pp, kBlock, k, quads);
                     if (mask) mask[ki * quads + qd] = acc;
                 }
                 const uint32_t pc = __popc(acc.x) + __popc(acc.y) + __popc(acc.z) + __popc(acc.w);
@@ -311,6 +320,145 @@ __global__ __launch_bounds__(kBlock) void k_bank_match(Src src, const uint4 *sli
             }
         }
         __syncthreads();  // the next round's positions must not overtake these reads
+    }
+}
+
+// ---------------------------------------------------------------- scoring a query (include/psk.h "score"; DESIGN.md 3.13 "Scoring a query")
+// k_bank_score: score[q][f] = the number of keys of query q whose k bits are all set in filter f.  The work item is (query, column chunk, part):
+// workgroup (x, y) walks the items (q, chunk) = x, x + gridDim.x, ... and takes the y-th of gridDim.y contiguous parts of the query's keys; a chunk
+// is up to kScoreChunkQuads 16-byte pieces of the slice rows (8192 filters), so the workgroup's uint32 counters are at most 32 KiB of LDS.  Per round
+// of KR keys (256; 128 where k > 32, so that positions + counters never pass 64 KiB): phase A as in k_bank_match, positions to LDS as pos[j][key];
+// phase B, G lanes per key, lane = one column piece, bank_row_and, and the 128 result bits go into the lane's vertical counters: kScorePlanes
+// bit-planes of a uint4, plane b = bit b of 128 running counts (a ripple add: carry = plane & x, plane ^= x, x = carry).  After 2^P - 1 keys, and at
+// the part's end, the planes are flushed into the LDS counters (ds_add of the non-zero values; lane l starts at bit l & 31, so that the 32 lanes of a
+// half-wave -- whose columns lie 128 words apart -- hit 32 different banks).  Then the counters go to scores: plain stores where the query is one
+// part (zeros included), atomicAdd of the non-zero ones onto the zeroed output otherwise.  Everything that decides a barrier (the item, the part's
+// bounds, the round) is uniform over the workgroup; phase B has no shuffle.
+constexpr uint32_t kScoreChunkQuads = 64, kScorePlanes = 6, kScoreFlushKeys = (1u << kScorePlanes) - 1;
+
+__device__ __forceinline__ void score_flush(uint32_t (&pl)[kScorePlanes][4], uint32_t *cnt, uint32_t rot)
+{
+    for (uint32_t s = 0; s < 32; ++s) {
+        const uint32_t bit = (s + rot) & 31;
+#pragma unroll
+        for (uint32_t c = 0; c < 4; ++c) {
+            uint32_t v = 0;
+#pragma unroll
+            for (uint32_t b = 0; b < kScorePlanes; ++b) v |= ((pl[b][c] >> bit) & 1u) << b;
+            if (v) atomicAdd(cnt + c * 32 + bit, v);  // ds_add_u32, no return value
+        }
+    }
+#pragma unroll
+    for (uint32_t b = 0; b < kScorePlanes; ++b) pl[b][0] = pl[b][1] = pl[b][2] = pl[b][3] = 0;
+}
+
+template <class Src, bool POW2>
+__global__ __launch_bounds__(kBlock) void k_bank_score(Src src, const uint4 *slices, uint32_t quads, Mod md, uint32_t k, uint64_t n, const uint64_t *qoff,
+                                                       uint64_t queries, uint64_t filters, uint32_t chunks, uint32_t KR, uint32_t *scores)
+{
+    extern __shared__ uint32_t score_lds[];  // counters [min(quads, 64) * 128], then pos [k][KR]
+    const uint32_t cwords = (quads < kScoreChunkQuads ? quads : kScoreChunkQuads) * 128u;
+    uint32_t *cnt = score_lds, *pos = score_lds + cwords;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kpw = KR >> 2;  // keys per wave and round
+    const uint32_t split = gridDim.y, part = blockIdx.y;
+    const uint64_t items = queries * chunks;
+    for (uint64_t w = blockIdx.x; w < items; w += gridDim.x) {
+        const uint64_t q = w / chunks;
+        const uint32_t q0 = (uint32_t)(w % chunks) * kScoreChunkQuads;                  // the chunk's first piece
+        const uint32_t cq = quads - q0 < kScoreChunkQuads ? quads - q0 : kScoreChunkQuads;  // ... and its pieces
+        uint64_t s0 = qoff[q], s1 = qoff[q + 1];
+        if (s1 > n) s1 = n;  // (no key is read at or beyond n whatever the offsets hold)
+        if (s0 > s1) s0 = s1;
+        const uint64_t per = (s1 - s0 + split - 1) / split;
+        const uint64_t a = s0 + per * part;
+        if (split > 1 && a >= s1) continue;  // an empty part of a query in parts: the entry point zeroed the output
+        const uint64_t b = a + per < s1 ? a + per : s1;
+        uint32_t lgG = 0;
+        while ((1u << lgG) < cq) ++lgG;
+        const uint32_t G = 1u << lgG, gl = lane & (G - 1), sub = lane >> lgG, slots = 64u >> lgG;
+        for (uint32_t i = threadIdx.x; i < cq * 128u; i += kBlock) cnt[i] = 0;
+        __syncthreads();
+        uint32_t pl[kScorePlanes][4] = {};
+        uint32_t pending = 0;
+        for (uint64_t base = a; base < b; base += KR) {
+            const uint64_t i = base + threadIdx.x;
+            if (threadIdx.x < KR && i < b) {
+                const typename Src::Key key = src.load(i);
+                for_each_hash(src, key, i, k, [&](uint32_t j, uint64_t h) { pos[j * KR + threadIdx.x] = bank_bit<POW2>(md, h); });
+            }
+            __syncthreads();
+            const uint64_t wbase = base + wave * kpw;
+            for (uint32_t t0 = 0; t0 < kpw && wbase + t0 < b; t0 += slots) {
+                const uint32_t t = t0 + sub;
+                if (t < kpw && wbase + t < b && gl < cq) {
+                    uint4 x = bank_row_and(slices + q0 + gl, pos + wave * kpw + t, KR, k, quads);
+#pragma unroll
+                    for (uint32_t p = 0; p < kScorePlanes; ++p) {
+                        const uint4 c = make_uint4(pl[p][0] & x.x, pl[p][1] & x.y, pl[p][2] & x.z, pl[p][3] & x.w);
+                        pl[p][0] ^= x.x, pl[p][1] ^= x.y, pl[p][2] ^= x.z, pl[p][3] ^= x.w;
+                        x = c;
+                    }
+                }
+                if (++pending == kScoreFlushKeys) {  // (uniform over the wave: a count of rounds, not of live keys)
+                    if (gl < cq) score_flush(pl, cnt + gl * 128u, lane & 31);
+                    pending = 0;
+                }
+            }
+            __syncthreads();  // the next round's positions must not overtake these reads
+        }
+        if (gl < cq) score_flush(pl, cnt + gl * 128u, lane & 31);
+        __syncthreads();
+        uint32_t *row = scores + q * filters;  // (64-bit: queries * filters may pass 2^32)
+        for (uint32_t i = threadIdx.x; i < cq * 128u; i += kBlock) {
+            const uint64_t f = (uint64_t)q0 * 128u + i;
+            if (f >= filters) break;
+            const uint32_t v = cnt[i];
+            if (split == 1) row[f] = v;
+            else if (v) atomicAdd(row + f, v);
+        }
+        __syncthreads();  // the next item's clear must not overtake this sweep
+    }
+}
+
+// k_bank_score_select: the filters of a row of finished scores that reach the row's threshold.  WAVE: a wave per row, four rows per workgroup
+// (rows of up to kScoreSelWaveCols columns); else a workgroup per row.  Rows beyond the grid are walked with a stride.  A pass over 64 (256)
+// columns: the ballot of score >= threshold gives a lane its rank among the pass's hits, the hits before the pass are a running sum (the workgroup
+// form adds the waves in front through LDS).  count: hits per row; ids / hit_scores: written at out_offs[row], ascending by column.
+constexpr uint32_t kScoreSelWaveCols = 2048;
+template <bool WAVE>
+__global__ __launch_bounds__(kBlock) void k_bank_score_select(const uint32_t *scores, uint64_t queries, uint64_t filters, const uint32_t *thr, uint32_t *count,
+                                                              const uint64_t *out_offs, uint32_t *ids, uint32_t *hit_scores)
+{
+    __shared__ uint32_t wsum[4];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t below = (1ULL << lane) - 1;
+    const uint64_t step = WAVE ? (uint64_t)gridDim.x * 4 : gridDim.x;
+    for (uint64_t q = WAVE ? (uint64_t)blockIdx.x * 4 + wave : blockIdx.x; q < queries; q += step) {  // (WAVE: uniform over the wave, no barrier below)
+        const uint32_t *row = scores + q * filters;
+        const uint32_t t = thr[q];
+        const uint64_t wr = ids ? out_offs[q] : 0;
+        uint64_t hits = 0;
+        for (uint64_t c0 = 0; c0 < filters; c0 += WAVE ? 64 : kBlock) {
+            const uint64_t f = c0 + (WAVE ? lane : threadIdx.x);
+            const uint32_t v = f < filters ? row[f] : 0;
+            const bool hit = f < filters && v >= t;
+            const uint64_t bal = __ballot(hit);
+            uint32_t before = 0, total = (uint32_t)__popcll(bal);
+            if (!WAVE) {
+                if (lane == 0) wsum[wave] = total;
+                __syncthreads();
+                for (uint32_t x = 0; x < wave; ++x) before += wsum[x];
+                total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+                __syncthreads();
+            }
+            if (hit && ids) {
+                const uint64_t o = wr + hits + before + (uint32_t)__popcll(bal & below);
+                ids[o] = (uint32_t)f;
+                if (hit_scores) hit_scores[o] = v;
+            }
+            hits += total;
+        }
+        if (count && (WAVE ? lane == 0 : threadIdx.x == 0)) count[q] = (uint32_t)hits;
     }
 }
 
@@ -659,6 +807,67 @@ extern "C" int psk_bank_match(const void *slices_dev, uint64_t filters, uint64_t
             });
         }));
     return finish(where, nullptr, st);
+}
+
+extern "C" int psk_bank_score(const void *slices_dev, uint64_t filters, uint64_t m_bits, uint32_t k, int layout, const void *data, const uint64_t *offsets, uint64_t n,
+                              uint32_t key_len, int where, const uint64_t *query_offsets_dev, uint64_t queries, uint32_t split, uint32_t *scores_dev, int device,
+                              void *stream)
+{
+    if (!slices_dev) return fail(PSK_EINVAL, "NULL slice image pointer");
+    PSK_TRY(bank_check_args(slices_dev, filters, m_bits, k, layout, n, key_len));
+    if (k > kBankMatchMaxK)
+        return fail(PSK_EINVAL, "psk_bank_score takes at most %u hashes (the positions of a round of keys live in LDS); %u were asked for", kBankMatchMaxK, k);
+    if (!query_offsets_dev || !scores_dev) return fail(PSK_EINVAL, "query_offsets_dev or scores_dev is NULL");
+    if (split < 1 || split > 65535) return fail(PSK_EINVAL, "split must be 1 .. 65535 workgroups per query; %u was passed", split);
+    if ((uintptr_t)slices_dev & 15) return fail(PSK_EINVAL, "the slice image must be 16-byte aligned");
+    if (queries == 0) return PSK_OK;
+    const uint64_t quads = psk_bank_slice_row_bytes(filters) / 16;
+    const uint64_t chunks = (quads + kScoreChunkQuads - 1) / kScoreChunkQuads;
+    const uint32_t KR = k <= 32 ? kBlock : kBlock / 2;  // positions + counters stay within 64 KiB of LDS
+    const size_t lds = ((size_t)(quads < kScoreChunkQuads ? quads : kScoreChunkQuads) * 128 + (size_t)k * KR) * 4;
+    bool pow2;
+    const Mod md = make_mod(m_bits, &pow2);
+    PSK_USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    if (split > 1 || n == 0) HIP_TRY(hipMemsetAsync(scores_dev, 0, (size_t)queries * filters * 4, st));
+    if (n == 0) return PSK_OK;  // (no keys: every row is zeros, no kernel)
+    ThreadStage &ts = thread_stage();
+    Batch b;
+    PSK_TRY(stage_batch(ts.keys, ts.offs, layout, data, offsets, n, key_len, where, st, &b));
+    const uint64_t items = queries * chunks;
+    const dim3 grid((unsigned)(items < kBankGridCap ? items : kBankGridCap), split);
+    PSK_TRY(with_source(b, [&](auto src) {
+        return with_pow2(pow2, [&](auto P) {
+            hipLaunchKernelGGL((k_bank_score<decltype(src), P.value>), grid, dim3(kBlock), lds, st, src, (const uint4 *)slices_dev, (uint32_t)quads, md, k, n,
+                               query_offsets_dev, queries, filters, (uint32_t)chunks, KR, scores_dev);
+            HIP_TRY(hipGetLastError());
+            return (int)PSK_OK;
+        });
+    }));
+    return finish(where, nullptr, st);
+}
+
+extern "C" int psk_bank_score_select(const uint32_t *scores_dev, uint64_t queries, uint64_t filters, const uint32_t *thresholds_dev, uint32_t *count_dev,
+                                     const uint64_t *out_offsets_dev, uint32_t *ids_dev, uint32_t *hit_scores_dev, int device, void *stream)
+{
+    if (!scores_dev || !thresholds_dev) return fail(PSK_EINVAL, "scores_dev or thresholds_dev is NULL");
+    if (filters == 0 || filters > (1ULL << 32)) return fail(PSK_EINVAL, "a bank holds 1 .. 2^32 filters; %llu were asked for", (unsigned long long)filters);
+    if (!count_dev && !ids_dev && !out_offsets_dev && !hit_scores_dev) return fail(PSK_EINVAL, "no output: pass count_dev, or ids_dev with out_offsets_dev");
+    if (!ids_dev != !out_offsets_dev) return fail(PSK_EINVAL, "ids_dev and out_offsets_dev go together");
+    if (hit_scores_dev && !ids_dev) return fail(PSK_EINVAL, "hit_scores_dev goes with ids_dev");
+    if (queries == 0) return PSK_OK;
+    PSK_USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    if (filters <= kScoreSelWaveCols) {
+        const uint64_t groups = (queries + 3) / 4;
+        hipLaunchKernelGGL(k_bank_score_select<true>, dim3((unsigned)(groups < kBankGridCap ? groups : kBankGridCap)), dim3(kBlock), 0, st, scores_dev, queries, filters,
+                           thresholds_dev, count_dev, out_offsets_dev, ids_dev, hit_scores_dev);
+    } else {
+        hipLaunchKernelGGL(k_bank_score_select<false>, dim3((unsigned)(queries < kBankGridCap ? queries : kBankGridCap)), dim3(kBlock), 0, st, scores_dev, queries, filters,
+                           thresholds_dev, count_dev, out_offsets_dev, ids_dev, hit_scores_dev);
+    }
+    HIP_TRY(hipGetLastError());
+    return PSK_OK;
 }
 
 // ---------------------------------------------------------------- bank statistics: bit counts, all-pairs overlap, row folds
