@@ -146,7 +146,7 @@ __global__ __launch_bounds__(kBlock) void k_qf_check_alt(psk::QfTable t, const u
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) out[i] = psk::qf_contains(t, hashes[i]) ? 1 : 0;
 }
 
-// ---- removal (psk_qf_remove_alt; q >= 5: a metadata word is 32 real slots)
+// ---- removal (psk_qf_remove_alt; q >= 5: a metadata word is 32 real slots; DESIGN.md "Quotient filter: removal", tests/qf_remove_model.py is this code step by step)
 // A cluster is a slot with shifted = 0 in use and the shifted slots behind it.  Taking elements out moves the rest of THEIR cluster left and
 // nothing else: the next cluster's head sits in its own quotient's slot and stays there.  So launch 1 marks, launch 2 repairs each marked cluster
 // by itself, in place.
