@@ -498,6 +498,60 @@ int psk_bank_overlap(const void *table_a_dev, uint64_t filters_a, const uint32_t
 int psk_bank_reduce(const void *src_dev, uint64_t filters, uint64_t m_bits, const uint64_t *seg_dev, const uint32_t *members_dev,
                     uint64_t groups, int op, void *dst_dev, uint64_t *bits_dev, int device, void *stream);
 
+/* ------------------------------------------------------ CountMinSketchBank
+ * Many small count-min sketches of ONE geometry (width, depth) in one table: `sketches` rows of psk_cms_table_bytes(width, depth) bytes each
+ * (4 * width * depth rounded up to 16), contiguous; row s is int32[depth][width], row-major by depth (bin = h_i % width + i * width,
+ * countminsketch.py:275); the pad ints of a row are never written.  Row s followed by the footer "IIq" (width, depth, elements_added[s]) is,
+ * byte for byte, the export of the reference's CountMinSketch(width, depth) after add(key, num_els) of the ops sent to s
+ * (countminsketch.py:257-288, 342-354).  Only adds enter a bank, with weights >= 0: every bin ends at min(old + the sum of the weights that
+ * reached it, INT32_MAX) in any order of execution.  elements_added is the caller's (one int64 per sketch).
+ * 1 <= width <= 2^31, 1 <= depth <= 64, n < 2^32 per call, PSK_KEYS_HASHES needs key_len >= depth; anything else is PSK_EINVAL.  build and reduce
+ * take rows of fewer than 2^32 ints (width * depth rounded up to 4; wider rows: PSK_EINVAL before anything is enqueued -- add and the checks carry
+ * 64-bit row sizes).  Byte offsets
+ * are 64-bit: sketches * row bytes may pass 2^32.  No handle: the caller owns the (device, 16-byte aligned) table; `data` / `offsets` /
+ * `ids` / `weights` / `out` follow `where`; the table, seg / perm / members, bound_dev, els_dev and saturated_dev are device memory.
+ *   bound_dev  int64[sketches] or NULL: the caller's upper bound on the largest value any bin of sketch s can hold AFTER this call (old bound
+ *          + the weights this call sends to s).  Where bound_dev[s] <= INT32_MAX an add to s is a plain no-return atomic add; otherwise, and
+ *          with bound_dev == NULL, it is the clamping compare-and-swap add of psk_cms_add.  A bound that is too low lets bins wrap.
+ *   saturated_dev  uint64 or NULL: raised by one for every clamping add that met the rail (a diagnostic, as PSK_CTR_SATURATED).
+ *   add    countminsketch.py:267-288 per row: sketch ids[i] gets key i with weight weights[i] (NULL: 1).  ids >= sketches are skipped, never
+ *          written.  A negative weight in a PSK_HOST batch is PSK_EINVAL before anything changes; in a PSK_DEVICE batch it is NOT checked and
+ *          counts as 0 (the caller validates device weights, as for psk_cbf_add_running).
+ *   check  out[i] = the reference's check of key i on sketch ids[i] under PSK_Q_MIN or PSK_Q_MEAN (sum // depth, Python floor), int32
+ *          (countminsketch.py:429-436); check_meanmin: the mean-min query (:438-453), int64, with elements_added read from els_dev[ids[i]]
+ *          on the device; width == 1 is PSK_EINVAL as for psk_cms_check_meanmin.  Both answer 0 for ids >= sketches.
+ *   build  keys grouped by sketch, device keys only: sketch s gets the keys at grouped positions [seg[s], seg[s+1]); position j is key
+ *          perm[j] (perm == NULL: key j) with weight weights_dev[perm[j]] (NULL: 1; negative: 0).  seg = uint64[sketches + 1] on the device,
+ *          non-decreasing, seg[sketches] <= n; whatever seg and perm hold, no key at or beyond n is read and no int outside the table is
+ *          written.  One workgroup per (sketch, part) counts in an LDS image of the row and adds every NON-ZERO counter to the row once --
+ *          plain or clamping by the rule of bound_dev; a zero counter is never touched.  The image holds rows of
+ *          width * depth <= 16384 ints.  A part takes it only where no 32-bit LDS counter can wrap: weights_dev == NULL, or
+ *          bound_dev[s] <= INT32_MAX; any other part adds straight to the row, clamping.  split: workgroups per sketch (1 .. 65535).
+ *          route: 0 = per part (the image unless keys * depth * 8 < the row's ints or the row is over the cap), 1 = the image wherever no
+ *          counter can wrap (rows over the cap: PSK_EINVAL), 2 = atomics straight into the row.  Enqueue only.
+ *   reduce row g of dst (`groups` rows of the table's row size) = the rows members[seg[g] .. seg[g + 1]) of src folded by the reference's join
+ *          (countminsketch.py:380-399), a left fold in member order per bin starting from an empty sketch: an accumulator on either rail
+ *          stays frozen, else acc = clamp(acc + b) computed in int64 -- exact for negative bins too.  els_out_dev[g] (int64, may be NULL) =
+ *          the same clamped fold of els_dev[member] (els_dev == NULL: zeros).  A member >= sketches counts as an empty sketch, an empty group
+ *          gives a zero row.  Rows are STORED.  dst overlapping src: PSK_EINVAL.  seg = uint64[groups + 1], non-decreasing; groups < 2^32;
+ *          groups and row pieces beyond the grid are walked with a stride.  Enqueue only. */
+int psk_cms_bank_add(void *table_dev, uint64_t sketches, uint64_t width, uint32_t depth, int layout, const void *data, const uint64_t *offsets,
+                     uint64_t n, uint32_t key_len, int where, const uint32_t *ids, const int32_t *weights, const int64_t *bound_dev,
+                     uint64_t *saturated_dev, int device, void *stream);
+int psk_cms_bank_check(const void *table_dev, uint64_t sketches, uint64_t width, uint32_t depth, int layout, const void *data,
+                       const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, const uint32_t *ids, int query, int32_t *out,
+                       int device, void *stream);
+int psk_cms_bank_check_meanmin(const void *table_dev, uint64_t sketches, uint64_t width, uint32_t depth, int layout, const void *data,
+                               const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, const uint32_t *ids,
+                               const int64_t *els_dev, int64_t *out, int device, void *stream);
+int psk_cms_bank_build(void *table_dev, uint64_t sketches, uint64_t width, uint32_t depth, int layout, const void *data,
+                       const uint64_t *offsets, uint64_t n, uint32_t key_len, const uint64_t *seg_dev, const uint32_t *perm_dev,
+                       const int32_t *weights_dev, const int64_t *bound_dev, uint64_t *saturated_dev, uint32_t split, int route, int device,
+                       void *stream);
+int psk_cms_bank_reduce(const void *src_dev, const int64_t *els_dev, uint64_t sketches, uint64_t width, uint32_t depth,
+                        const uint64_t *seg_dev, const uint32_t *members_dev, uint64_t groups, void *dst_dev, int64_t *els_out_dev, int device,
+                        void *stream);
+
 /* ------------------------------------------------------------ CuckooFilter
  * cuckoo/cuckoo.py: `capacity` buckets of `bucket_size` fingerprints of `fp_bits` bits.  No handle: the caller owns (device memory)
  *   buckets   uint32[capacity][bucket_size], every row filled from the left, its unused slots 0 (an export is this array plus the footer)

@@ -7,6 +7,7 @@ the work is done by hand-written gfx950 HIP kernels behind the C ABI in ``includ
 """
 
 from .bank import BloomFilterBank
+from .cmsbank import CountMinSketchBank
 from .bloom import BloomFilter
 from .countingbloom import CountingBloomFilter
 from .countminsketch import CountMeanMinSketch, CountMeanSketch, CountMinSketch, HeavyHitters, StreamThreshold
@@ -32,6 +33,7 @@ __version__ = "0.1.0"
 __all__ = [
     "BloomFilter",
     "BloomFilterBank",
+    "CountMinSketchBank",
     "CountingBloomFilter",
     "CountMinSketch",
     "CountMeanSketch",

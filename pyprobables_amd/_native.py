@@ -96,6 +96,11 @@ PROTOTYPES = {
     "psk_bank_popcount": (_int, [_vp, _u64, _u64, _vp, _u64, _vp, _int, _vp]),
     "psk_bank_overlap": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _vp, _int, _vp]),
     "psk_bank_reduce": (_int, [_vp, _u64, _u64, _vp, _vp, _u64, _int, _vp, _vp, _int, _vp]),
+    "psk_cms_bank_add": (_int, [_vp, _u64, _u64, _u32, *_KEYS, _int, _vp, _vp, _vp, _vp, _int, _vp]),
+    "psk_cms_bank_check": (_int, [_vp, _u64, _u64, _u32, *_KEYS, _int, _vp, _int, _vp, _int, _vp]),
+    "psk_cms_bank_check_meanmin": (_int, [_vp, _u64, _u64, _u32, *_KEYS, _int, _vp, _vp, _vp, _int, _vp]),
+    "psk_cms_bank_build": (_int, [_vp, _u64, _u64, _u32, *_KEYS, _vp, _vp, _vp, _vp, _vp, _u32, _int, _int, _vp]),
+    "psk_cms_bank_reduce": (_int, [_vp, _vp, _u64, _u64, _u32, _vp, _vp, _u64, _vp, _vp, _int, _vp]),
     "psk_ck_triples": (_int, [_u64, _u32, *_KEYS, _int, _vp, _int, _vp]),
     "psk_ck_check": (_int, [_u64, _u32, _u32, _vp, _vp, *_KEYS, _int, _vp, _int, _vp]),
     "psk_ck_present": (_int, [_u64, _u32, _vp, _vp, _vp, _u64, _vp, _int, _vp]),

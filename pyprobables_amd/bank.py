@@ -116,7 +116,90 @@ def _slice_batch(b: KeyBatch, lo: int, hi: int) -> KeyBatch:
     return KeyBatch(b.layout, b.data + int(offs[lo]) * _ELEM[b.layout], o.ctypes.data, hi - lo, 0, b.where, b.device, [*b.keep, o])
 
 
-class BloomFilterBank(DeviceResident):
+class RowBank(DeviceResident):
+    """what the banks share (BloomFilterBank here, CountMinSketchBank in cmsbank.py): ``_num_rows`` rows of one geometry in one device table, row
+    ids and row offsets that arrive as arrays or tensors on either side, and the split of a grouped build.  A subclass sets ``_ROW`` (what the
+    messages call a row), ``_num_rows``, ``_device``, ``_cus`` and ``_split``."""
+
+    _NOUN = "bank"
+    _ROW = "row"
+
+    def _index(self, f) -> int:
+        f = int(f)
+        if not 0 <= f < self._num_rows:
+            raise IndexError(f"{self._ROW} {f} out of range [0, {self._num_rows})")
+        return f
+
+    def _ids(self, ids, n: int, where: int, validate: bool):
+        """-> the ids where the keys are: an int64 numpy array (host keys) or an int64 tensor (device keys), checked"""
+        is_dev = torch is not None and isinstance(ids, torch.Tensor) and ids.is_cuda
+        if is_dev:
+            if ids.dim() != 1 or ids.is_floating_point() or ids.dtype == torch.bool:
+                raise TypeError("ids must be a 1-D integer tensor")
+            if ids.numel() != n:
+                raise ValueError("ids length differs from the number of keys")
+            if ids.device.index != self._device:
+                raise ValueError(f"ids live on cuda:{ids.device.index}, the bank on cuda:{self._device}")
+            if validate and n:  # one reduction, one synchronisation
+                lo, hi = torch.aminmax(ids)
+                if int(lo.item()) < 0 or int(hi.item()) >= self._num_rows:
+                    raise ValueError(f"{self._ROW} ids must lie in [0, {self._num_rows})")
+            return ids.to(torch.int64) if where == N.DEVICE else ids.cpu().numpy().astype(np.int64)
+        a = ids.numpy() if torch is not None and isinstance(ids, torch.Tensor) else np.asarray(ids)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise TypeError("ids must be a 1-D integer array")
+        if a.size != n:
+            raise ValueError("ids length differs from the number of keys")
+        a = a.astype(np.int64, copy=False)
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= self._num_rows):  # host ids are always checked
+            raise ValueError(f"{self._ROW} ids must lie in [0, {self._num_rows})")
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self._dev) if where == N.DEVICE else a
+
+    def _offsets(self, offs, n: int, where: int, validate: bool, count=None, what: str = "filter_offsets"):
+        """offsets[count + 1] (filter_offsets / sketch_offsets: count = the bank's rows; query_offsets: any count >= 0, None) -> as _ids: where the keys are, checked
+        (non-decreasing, from 0 to n)"""
+        is_dev = torch is not None and isinstance(offs, torch.Tensor) and offs.is_cuda
+        want = f"{count + 1} integers" if count is not None else "a 1-D integer array of queries + 1 entries"
+        size = int(offs.numel()) if torch is not None and isinstance(offs, torch.Tensor) else None
+        if is_dev:
+            if offs.dim() != 1 or size < 1 or (count is not None and size != count + 1) or offs.is_floating_point() or offs.dtype == torch.bool:
+                raise TypeError(f"{what} must be {want}")
+            if offs.device.index != self._device:
+                raise ValueError(f"{what} live on cuda:{offs.device.index}, the bank on cuda:{self._device}")
+            o = offs.to(torch.int64).contiguous()
+            if validate:  # one reduction, one synchronisation
+                bad = (o[1:] < o[:-1]).any() | (o[0] != 0) | (o[-1] != n)
+                if bool(bad.item()):
+                    raise ValueError(f"{what} must be non-decreasing, start at 0 and end at the number of keys")
+            return o if where == N.DEVICE else o.cpu().numpy()
+        a = offs.numpy() if torch is not None and isinstance(offs, torch.Tensor) else np.asarray(offs)
+        if a.ndim != 1 or a.size < 1 or (count is not None and a.size != count + 1) or a.dtype.kind not in "iu":
+            raise TypeError(f"{what} must be {want}")
+        a = np.ascontiguousarray(a.astype(np.int64, copy=False))
+        if (np.diff(a) < 0).any() or int(a[0]) != 0 or int(a[-1]) != n:
+            raise ValueError(f"{what} must be non-decreasing, start at 0 and end at the number of keys")
+        return torch.from_numpy(a).to(self._dev) if where == N.DEVICE else a
+
+    @staticmethod
+    def _addr(x) -> int:
+        if isinstance(x, np.ndarray):
+            return x.ctypes.data if x.size else 0
+        return x.data_ptr() if x.numel() else 0
+
+    def _ids_u32(self, ids):
+        """int64 ids -> the uint32 words the engine reads (fewer than 2^31 rows: the low word)"""
+        if isinstance(ids, np.ndarray):
+            return np.ascontiguousarray(ids.astype(np.uint32))
+        return ids.to(torch.int32).contiguous()
+
+    def split_for(self) -> int:
+        """workgroups per row of a grouped build: 1 unless the bank has fewer than twice as many rows as the device has CUs"""
+        if self._split is not None:
+            return int(self._split)
+        return 1 if self._num_rows >= 2 * self._cus else -(-2 * self._cus // self._num_rows)
+
+
+class BloomFilterBank(RowBank):
     """``num_filters`` Bloom filters sized by ``(est_elements, false_positive_rate)`` as the reference sizes one (bloom.py:463-502).
 
     Keys are accepted as everywhere in the package (lists of ``str`` / ``bytes``, ``(n, L)`` uint8 arrays or tensors, ragged
@@ -124,7 +207,8 @@ class BloomFilterBank(DeviceResident):
     evaluated on the host (the digest families on the device) and travels as pre-computed hashes, as in :class:`BloomFilter`."""
 
     _CHUNK = 2**32 - 1  # keys per engine call
-    _NOUN = "bank"
+    _ROW = "filter"
+    _num_rows = property(lambda self: self._num_filters)
 
     def __init__(self, num_filters, est_elements, false_positive_rate, hash_function=None, device=None):
         if not (isinstance(num_filters, (int, np.integer)) and 0 < int(num_filters) < 2**31):
@@ -186,83 +270,9 @@ class BloomFilterBank(DeviceResident):
             self._els[self._index(f)] = 0
             self._mark_stale(self._index(f))
 
-    def _index(self, f) -> int:
-        f = int(f)
-        if not 0 <= f < self._num_filters:
-            raise IndexError(f"filter {f} out of range [0, {self._num_filters})")
-        return f
-
     # ------------------------------------------------------------------ batches, ids, offsets
     def _batch(self, keys) -> KeyBatch:
         return self._same_device(hashed_batch(keys, self._hash_func, self._is_fused, self._digest, self._number_hashes, self._device, self._stream))
-
-    def _ids(self, ids, n: int, where: int, validate: bool):
-        """-> the ids where the keys are: an int64 numpy array (host keys) or an int64 tensor (device keys), checked"""
-        is_dev = torch is not None and isinstance(ids, torch.Tensor) and ids.is_cuda
-        if is_dev:
-            if ids.dim() != 1 or ids.is_floating_point() or ids.dtype == torch.bool:
-                raise TypeError("ids must be a 1-D integer tensor")
-            if ids.numel() != n:
-                raise ValueError("ids length differs from the number of keys")
-            if ids.device.index != self._device:
-                raise ValueError(f"ids live on cuda:{ids.device.index}, the bank on cuda:{self._device}")
-            if validate and n:  # one reduction, one synchronisation
-                lo, hi = torch.aminmax(ids)
-                if int(lo.item()) < 0 or int(hi.item()) >= self._num_filters:
-                    raise ValueError(f"filter ids must lie in [0, {self._num_filters})")
-            return ids.to(torch.int64) if where == N.DEVICE else ids.cpu().numpy().astype(np.int64)
-        a = ids.numpy() if torch is not None and isinstance(ids, torch.Tensor) else np.asarray(ids)
-        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
-            raise TypeError("ids must be a 1-D integer array")
-        if a.size != n:
-            raise ValueError("ids length differs from the number of keys")
-        a = a.astype(np.int64, copy=False)
-        if a.size and (int(a.min()) < 0 or int(a.max()) >= self._num_filters):  # host ids are always checked
-            raise ValueError(f"filter ids must lie in [0, {self._num_filters})")
-        return torch.from_numpy(np.ascontiguousarray(a)).to(self._dev) if where == N.DEVICE else a
-
-    def _offsets(self, offs, n: int, where: int, validate: bool, count=None, what: str = "filter_offsets"):
-        """offsets[count + 1] (filter_offsets: count = num_filters; query_offsets: any count >= 0, None) -> as _ids: where the keys are, checked
-        (non-decreasing, from 0 to n)"""
-        is_dev = torch is not None and isinstance(offs, torch.Tensor) and offs.is_cuda
-        want = f"{count + 1} integers" if count is not None else "a 1-D integer array of queries + 1 entries"
-        size = int(offs.numel()) if torch is not None and isinstance(offs, torch.Tensor) else None
-        if is_dev:
-            if offs.dim() != 1 or size < 1 or (count is not None and size != count + 1) or offs.is_floating_point() or offs.dtype == torch.bool:
-                raise TypeError(f"{what} must be {want}")
-            if offs.device.index != self._device:
-                raise ValueError(f"{what} live on cuda:{offs.device.index}, the bank on cuda:{self._device}")
-            o = offs.to(torch.int64).contiguous()
-            if validate:  # one reduction, one synchronisation
-                bad = (o[1:] < o[:-1]).any() | (o[0] != 0) | (o[-1] != n)
-                if bool(bad.item()):
-                    raise ValueError(f"{what} must be non-decreasing, start at 0 and end at the number of keys")
-            return o if where == N.DEVICE else o.cpu().numpy()
-        a = offs.numpy() if torch is not None and isinstance(offs, torch.Tensor) else np.asarray(offs)
-        if a.ndim != 1 or a.size < 1 or (count is not None and a.size != count + 1) or a.dtype.kind not in "iu":
-            raise TypeError(f"{what} must be {want}")
-        a = np.ascontiguousarray(a.astype(np.int64, copy=False))
-        if (np.diff(a) < 0).any() or int(a[0]) != 0 or int(a[-1]) != n:
-            raise ValueError(f"{what} must be non-decreasing, start at 0 and end at the number of keys")
-        return torch.from_numpy(a).to(self._dev) if where == N.DEVICE else a
-
-    @staticmethod
-    def _addr(x) -> int:
-        if isinstance(x, np.ndarray):
-            return x.ctypes.data if x.size else 0
-        return x.data_ptr() if x.numel() else 0
-
-    def _ids_u32(self, ids):
-        """int64 ids -> the uint32 words the engine reads (num_filters < 2^31: the low word)"""
-        if isinstance(ids, np.ndarray):
-            return np.ascontiguousarray(ids.astype(np.uint32))
-        return ids.to(torch.int32).contiguous()
-
-    def split_for(self) -> int:
-        """workgroups per filter of a grouped build: 1 unless the bank has fewer than twice as many filters as the device has CUs"""
-        if self._split is not None:
-            return int(self._split)
-        return 1 if self._num_filters >= 2 * self._cus else -(-2 * self._cus // self._num_filters)
 
     def _grouped_pays(self, n: int) -> bool:
         """the automatic choice for device keys with ids: sort + grouped build from BANK_GROUP_MIN_KEYS keys on, where a filter's mean share of

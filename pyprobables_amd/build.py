@@ -27,12 +27,12 @@ VARIANT_SOURCES = [
     "psk_part_cbf_multi.hip",
     "psk_part_cbf_window.hip",
 ]
-PLAIN_SOURCES = ["psk_cbf.hip", "psk_cms.hip", "psk_bloom.hip", "psk_bloom_ordered.hip", "psk_hash.hip", "psk_cuckoo.hip", "psk_counting_cuckoo.hip", "psk_quotient.hip", "psk_bank.hip", "psk_capi.hip", "psk_index_ops.hip", "psk_segscan.hip", "psk_running.hip", "psk_cbf_running.hip", "psk_stage.hip",
+PLAIN_SOURCES = ["psk_cbf.hip", "psk_cms.hip", "psk_bloom.hip", "psk_bloom_ordered.hip", "psk_hash.hip", "psk_cuckoo.hip", "psk_counting_cuckoo.hip", "psk_quotient.hip", "psk_bank.hip", "psk_cms_bank.hip", "psk_capi.hip", "psk_index_ops.hip", "psk_segscan.hip", "psk_running.hip", "psk_cbf_running.hip", "psk_stage.hip",
                  "psk_merge.hip", "psk_table_ops.hip", "psk_part_dispatch.hip"]
 # (source, object stem, extra flags); the heaviest units first so that the pool stays busy to the end
 SOURCES = [(f, Path(f).stem + f"_v{v}", [f"-DPSK_TU_POW2={v}"]) for f in VARIANT_SOURCES for v in (1, 0)] + \
           [(f, Path(f).stem, []) for f in PLAIN_SOURCES]
-HEADERS = ["psk_device.hpp", "psk_partition.hpp", "psk_host.hpp", "psk_part_counter.hpp", "psk_lookup.hpp", "psk_part_lookup.hpp", "psk_nibble.hpp", "psk_nibble_pipe.hpp", "psk_window.hpp", "psk_digest.hpp", "psk_segscan.hpp", "psk_running.hpp", "psk_cbf_running.hpp", "psk_cbf_running_layout.hpp", "psk_quotient.hpp", "psk_cuckoo.hpp", "psk_stage.hpp",
+HEADERS = ["psk_device.hpp", "psk_partition.hpp", "psk_host.hpp", "psk_part_counter.hpp", "psk_lookup.hpp", "psk_part_lookup.hpp", "psk_nibble.hpp", "psk_nibble_pipe.hpp", "psk_window.hpp", "psk_digest.hpp", "psk_segscan.hpp", "psk_running.hpp", "psk_cbf_running.hpp", "psk_cbf_running_layout.hpp", "psk_quotient.hpp", "psk_cuckoo.hpp", "psk_stage.hpp", "psk_bank_stage.hpp",
            "../../include/psk.h"]
 OUT = CSRC / "libpsk_hip.so"
 OBJ = CSRC / "build"

@@ -58,26 +58,29 @@ class CountMinSketch:
         if filepath is not None and _existing_file(filepath):
             self._parse_bytes(Path(filepath).expanduser().resolve().read_bytes())
             return
+        self._width, self._depth, self._confidence, self._error_rate = self._geometry(width, depth, confidence, error_rate)
+        self._tab = DeviceTable("cms", self._width, self._depth, self._dev_arg)
+
+    @staticmethod
+    def _geometry(width, depth, confidence, error_rate):
+        """-> (width, depth, confidence, error_rate) from either pair, as the reference sizes a sketch (countminsketch.py:88-113)"""
         if width is not None and depth is not None:
             if not (isinstance(width, Number) and width > 0 and isinstance(depth, Number) and depth > 0):
                 raise InitializationError("CountMinSketch: width and depth must be greater than 0")
-            self._width, self._depth = int(width), int(depth)
-            self._confidence = 1 - (1 / math.pow(2, self._depth))
-            self._error_rate = 2 / self._width
-        elif confidence is not None and error_rate is not None:
+            width, depth = int(width), int(depth)
+            return width, depth, 1 - (1 / math.pow(2, depth)), 2 / width
+        if confidence is not None and error_rate is not None:
             if not (isinstance(confidence, Number) and confidence > 0 and isinstance(error_rate, Number) and error_rate > 0):
                 raise InitializationError("CountMinSketch: width and depth must be greater than 0")
-            self._confidence, self._error_rate = confidence, error_rate
-            self._width = math.ceil(2 / error_rate)                                   # countminsketch.py:102
-            self._depth = math.ceil((-1 * math.log(1 - confidence)) / 0.6931471805599453)  # :103-104
-        else:
-            raise InitializationError(
-                "Must provide one of the following to initialize the Count-Min Sketch:\n"
-                "    A file to load,\n"
-                "    The width and depth,\n"
-                "    OR confidence and error rate"
-            )
-        self._tab = DeviceTable("cms", self._width, self._depth, self._dev_arg)
+            width = math.ceil(2 / error_rate)                                   # countminsketch.py:102
+            depth = math.ceil((-1 * math.log(1 - confidence)) / 0.6931471805599453)  # :103-104
+            return width, depth, confidence, error_rate
+        raise InitializationError(
+            "Must provide one of the following to initialize the Count-Min Sketch:\n"
+            "    A file to load,\n"
+            "    The width and depth,\n"
+            "    OR confidence and error rate"
+        )
 
     # ------------------------------------------------------------------ properties
     @property

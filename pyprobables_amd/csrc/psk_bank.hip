@@ -10,7 +10,7 @@
 //                                   into bit-plane counters in registers), and the filters of each query that reach a threshold
 //   psk_bank_popcount / psk_bank_overlap / psk_bank_reduce  the filters as sets: bits per row, popcount(a AND b) for all pairs (a tiled GEMM over
 //                                   (AND, popcount-add)), and the OR / AND of groups of rows stored as a new table
-#include "psk_stage.hpp"
+#include "psk_bank_stage.hpp"
 
 namespace {
 
@@ -150,31 +150,6 @@ int bank_check_args(const void *table_dev, uint64_t filters, uint64_t m_bits, ui
     if (n >> 32) return fail(PSK_EINVAL, "a bank call takes fewer than 2^32 keys; %llu were passed", (unsigned long long)n);
     if (layout == PSK_KEYS_HASHES && key_len < k) return fail(PSK_EINVAL, "pre-hashed batch carries %u hashes per key, the bank needs %u", key_len, k);
     return PSK_OK;
-}
-
-// the staged filter ids of a PSK_HOST call: the one buffer a bank call needs beside ThreadStage's three
-DevBuf &bank_ids_stage()
-{
-    static thread_local DevBuf ids;
-    return ids;
-}
-
-// One keyed bank call: on `device`, stage the batch, its ids and out[out_bytes] (none: an update), run launch(src, ids_dev, out_dev, stream), end the call.
-template <class Launch>
-int bank_keyed_call(int layout, const void *data, const uint64_t *offsets, uint64_t n, uint32_t key_len, int where, const uint32_t *ids, void *out,
-                    uint64_t out_bytes, int device, void *stream, Launch &&launch)
-{
-    PSK_USE_DEVICE(device);
-    hipStream_t st = (hipStream_t)stream;
-    ThreadStage &ts = thread_stage();
-    Batch b;
-    PSK_TRY(stage_batch(ts.keys, ts.offs, layout, data, offsets, n, key_len, where, st, &b));
-    const uint32_t *ids_dev = nullptr;
-    PSK_TRY(stage_vec(bank_ids_stage(), ids, n, where, st, &ids_dev));
-    OutBuf o;
-    PSK_TRY(stage_out(ts.out, out, out_bytes, where, &o));
-    if (n) PSK_TRY(with_source(b, [&](auto src) { return launch(src, ids_dev, o.dev, st); }));
-    return finish(where, out_bytes ? &o : nullptr, st);
 }
 
 // ---------------------------------------------------------------- the slice image (include/psk.h "slice image")
